@@ -21,6 +21,12 @@ Weak scaling: every GPU owns ``--flows-per-gpu`` synthetic flows (default 12.5M,
 BASELINE config "Netflow 100M flows, 20 topics, DP=8"). Synthetic data with random-init topic
 priors (oni355.synth.flow), random-init LDA. ``--gpus N`` outside torchrun re-launches itself
 under ``torch.distributed.run`` (a child process, started before anything touches the GPU).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the JSON line. ``--full`` adds
+the measurements that take runs of their own (the realistic-vocabulary day, ``realistic_vocab`` in
+the JSON line). ``--dump-outputs DIR`` writes the arrays the last timed step returned as
+``DIR/<name>.npy``: the day is generated from ``--seed`` and the chain is a pure function of (data,
+seed, sweep), so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -78,9 +84,16 @@ def parse(argv=None):
                     help="every step reads its day from the columnar store (memory-mapped read + IPv6 keying + "
                          "pinned copy on a loader thread, overlapping the previous day) -- what oni-ml does day "
                          "after day (pipeline.daily); the store is written once at setup")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the measurements that take runs of their own (today: the "
+                         "realistic-vocabulary day, --realistic-steps); a plain run times the headline only")
     ap.add_argument("--realistic-steps", type=int, default=3,
-                    help="after the headline, also time this many steps (1 warm-up) of the realistic-vocabulary "
-                         "day of the same size and report them under 'realistic_vocab' (0: skip)")
+                    help="--full: after the headline, also time this many steps (1 warm-up) of the realistic-"
+                         "vocabulary day of the same size and report them under 'realistic_vocab' (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (result "
+                         "rows, scores, word keys, θ, φ, topic counts) as DIR/<name>.npy in float32 / float64 "
+                         "(rank 0's view; tables past the size cap as a fixed seeded sample of their rows)")
     a = ap.parse_args(argv)
     for kv in a.env:
         k, _, v = kv.partition("=")
@@ -134,13 +147,13 @@ def main(argv=None) -> int:
         os.environ["ONI_NO_GRAPH"] = "1"
     comm = pc.init_from_env(a.device)
     out = run_sweep_mode(a, comm) if a.mode == "sweep" else run_pipeline_mode(a, comm)
-    if (a.mode == "pipeline" and a.realistic_steps > 0 and not a.realistic_vocab and not a.from_pcap
+    if (a.full and a.mode == "pipeline" and a.realistic_steps > 0 and not a.realistic_vocab and not a.from_pcap
             and not a.from_store):
         # the same day shape with a long-tail vocabulary (V ~ 4e5 flow words: the q table leaves
         # L2), reported next to the headline, not instead of it
         import copy
         b = copy.copy(a)
-        b.realistic_vocab, b.steps, b.warmup = True, a.realistic_steps, 1
+        b.realistic_vocab, b.steps, b.warmup, b.dump_outputs = True, a.realistic_steps, 1, None
         r = run_pipeline_mode(b, comm)
         out["realistic_vocab"] = {k: r[k] for k in ("value", "ms_per_step", "ms_per_sweep_in_training", "vocab",
                                                     "tokens", "planted_anomaly_recall_topN", "steps", "warmup",
@@ -160,6 +173,53 @@ def _sync(dev):
 def _median_timings(per_step: list[dict]) -> dict:
     keys = [k for k in per_step[0] if k.endswith("_s")]
     return {k: round(statistics.median(t[k] for t in per_step), 5) for k in keys}
+
+
+DUMP_TABLE_BYTES = 24 << 20  # cap of θ and of φ in a dump; everything else is a few hundred KB (64 MB in all)
+
+
+def _dump_table(t, cap: int = DUMP_TABLE_BYTES) -> np.ndarray:
+    """A [rows, cols] device table as float32 on the host; past ``cap`` bytes a fixed seeded sample of
+    its rows (ascending row order, the same rows for the same shape in every run)."""
+    import torch
+    row_bytes = max(int(t.shape[1]) * 4, 1)
+    if t.shape[0] * row_bytes > cap:
+        keep = np.sort(np.random.default_rng(0).choice(int(t.shape[0]), cap // row_bytes, replace=False))
+        t = t[torch.from_numpy(keep).to(t.device)]
+    return t.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(path: str, comm, res, model) -> None:
+    """``--dump-outputs``: the arrays the timed path handed to its caller in its last step, one
+    ``<name>.npy`` each in float32 / float64 (integers exactly: row ids and 32-bit word keys as
+    float64, 64-bit word keys as their high and low halves). Written by rank 0 (the result rows
+    are global; θ is this rank's documents)."""
+    out = {}
+    if res is not None:
+        for name in ("rows", "scores", "src_scores", "dst_scores", "src_words", "dst_words", "words"):
+            x = getattr(res, name, None)
+            if x is None:
+                continue
+            x = np.asarray(x)
+            if x.dtype.kind in "iu" and x.dtype.itemsize == 8 and name != "rows":
+                u = x.astype(np.uint64)
+                out[name + "_hi"] = (u >> np.uint64(32)).astype(np.float64)
+                out[name + "_lo"] = (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            elif x.dtype.kind in "iu":
+                assert x.size == 0 or int(np.abs(x).max()) < 2**53, name
+                out[name] = x.astype(np.float64)
+            else:
+                out[name] = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+    out["theta"] = _dump_table(model.theta())
+    out["phi"] = _dump_table(model.phi())
+    out["topic_counts"] = model.nk_cur[: model.K].cpu().numpy().astype(np.float64)
+    if model.likelihoods:
+        out["loglik"] = np.asarray([model.likelihoods[-1][1]], dtype=np.float64)
+    if comm.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -344,6 +404,9 @@ def run_pipeline_mode(a, comm) -> dict:
     baseline_cfg = {"flow": "Netflow 100M flows, 20 topics, DP=8 (N=8); weak-scaled 12.5M flows/GPU",
                     "dns": "DNS suspicious-connects (pcap->word pipeline), 50 topics",
                     "proxy": "proxy suspicious-connects"}[a.source]
+    hbm_peak = torch.cuda.max_memory_allocated(dev) if dev.type == "cuda" else None  # of the steps, not the dump
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, comm, res, model)
     return {
         "metric": metric,
         "value": round(value, 1),
@@ -391,7 +454,7 @@ def run_pipeline_mode(a, comm) -> dict:
         # count magnitudes (the int32 tables' headroom) and the device memory high-water mark
         "max_topic_share": round(float(model.nk_cur[:K].max()) / max(model.T_global, 1), 4),
         "min_score_topN": float(res.scores[0]) if len(res.scores) else None,
-        "hbm_peak_gb": (round(torch.cuda.max_memory_allocated(dev) / 2**30, 2) if dev.type == "cuda" else None),
+        "hbm_peak_gb": round(hbm_peak / 2**30, 2) if hbm_peak is not None else None,
     }
 
 
@@ -419,6 +482,8 @@ def run_sweep_mode(a, comm) -> dict:
     _sync(dev)
     dt = comm.allreduce_scalar(time.perf_counter() - t0, "max")
     tokens = int(comm.allreduce_scalar(su.run.corpus.T, "sum"))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, comm, None, model)  # a sweep returns nothing: the model's tables
     return {
         "metric": f"{a.source} record-sweeps/sec (whole node), {a.topics}-topic collapsed-Gibbs LDA",
         "value": round(su.n_total * a.steps / dt, 1),

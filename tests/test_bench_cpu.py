@@ -27,7 +27,7 @@ def _run(cmd):
     return json.loads(lines[0])
 
 
-def _check(out, n):
+def _check(out, n, full=True):
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         base = json.load(f)
     assert out["metric"] == base["metric"]
@@ -41,24 +41,60 @@ def _check(out, n):
         assert stage in out["stage_median_s"], stage
     assert out["gibbs_iters_per_sec"] > 0 and out["config"]["sweeps_per_step"] == 6
     assert out["vs_baseline"] is None
-    # the realistic-vocabulary day of the same shape is reported next to the headline
+    # --full: the realistic-vocabulary day of the same shape is reported next to the headline; a
+    # plain run times the headline alone
+    if not full:
+        assert "realistic_vocab" not in out
+        return
     rv = out["realistic_vocab"]
     assert rv["value"] > 0 and rv["steps"] == 3 and rv["vocab"] > 0 and 0.0 <= rv["planted_anomaly_recall_topN"] <= 1.0
 
 
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    """One plain run (no --full) with --dump-outputs, shared by the tests that compare against it."""
+    d = str(tmp_path_factory.mktemp("dump_plain"))
+    return _run([sys.executable, "bench.py", *ARGS, "--dump-outputs", d]), _load_dump(d)
+
+
 def test_bench_single_process():
-    _check(_run([sys.executable, "bench.py", *ARGS]), 1)
+    _check(_run([sys.executable, "bench.py", *ARGS, "--full"]), 1)
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_repeatably(plain_run, tmp_path):
+    """A plain run reports the headline alone; --dump-outputs writes the last timed step's result
+    arrays and model tables as float32 / float64 .npy, identical from run to run."""
+    import numpy as np
+    out, dump = plain_run
+    _check(out, 1, full=False)
+    assert {"rows", "scores", "src_scores", "dst_scores", "src_words", "dst_words", "theta", "phi", "topic_counts",
+            "loglik"} <= set(dump)
+    assert all(x.dtype in (np.float32, np.float64) for x in dump.values())
+    assert sum(x.nbytes for x in dump.values()) <= 64 << 20
+    assert dump["rows"].size == dump["scores"].size > 0 and np.all(np.diff(dump["scores"]) >= 0)
+    assert dump["theta"].shape[0] == out["docs_local"] and dump["phi"].shape[0] == out["vocab"]
+    assert dump["topic_counts"].sum() == out["tokens"] and dump["loglik"][0] == out["loglik"]
+    again_out = _run([sys.executable, "bench.py", *ARGS, "--dump-outputs", str(tmp_path)])
+    again = _load_dump(str(tmp_path))
+    assert set(again) == set(dump) and again_out["loglik"] == out["loglik"]
+    for k in dump:
+        assert np.array_equal(dump[k], again[k]), k
 
 
 def test_bench_self_launches_ranks():
     """``bench.py --gpus 2`` outside torchrun starts its own 2-rank torch.distributed.run child."""
-    _check(_run([sys.executable, "bench.py", "--gpus", "2", *ARGS]), 2)
+    _check(_run([sys.executable, "bench.py", "--gpus", "2", *ARGS, "--full"]), 2)
 
 
 @pytest.mark.slow
 def test_bench_two_ranks_torchrun():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr=127.0.0.1", f"--master-port={_port()}", "bench.py", "--gpus", "2", *ARGS]
+           "--master-addr=127.0.0.1", f"--master-port={_port()}", "bench.py", "--gpus", "2", *ARGS, "--full"]
     _check(_run(cmd), 2)
 
 
@@ -94,11 +130,11 @@ def test_combined_bench_cpu_and_sizing():
     assert not sizing.plan("flow", 20 * 10**9, 100, 10**6, 10**6).fits()
 
 
-def test_bench_forced_one_rank_process_group_matches_plain():
+def test_bench_forced_one_rank_process_group_matches_plain(plain_run):
     """ONI_FORCE_DIST=1 drives every collective through a real 1-rank process group (the RCCL code
     path on a single GPU box; gloo here): same model and results as the collective-free run."""
-    plain = _run([sys.executable, "bench.py", *ARGS])
-    env_cmd = [sys.executable, "bench.py", *ARGS]
+    plain = plain_run[0]
+    env_cmd = [sys.executable, "bench.py", *ARGS, "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", PYTHONUNBUFFERED="1", ONI_FORCE_DIST="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()))
     r = subprocess.run(env_cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

@@ -23,14 +23,16 @@ def _read(p):
 
 
 def test_forwarded_day_matches_local_run(tmp_path):
-    sock = str(tmp_path / "mld.sock")
+    # service and client both run in tmp_path and name the socket relative to it: a Unix socket
+    # address holds ~107 bytes, which a deep temporary directory's absolute path can exceed
+    sock = "mld.sock"
     env = dict(os.environ, PYTHONPATH=ROOT)
     srv = subprocess.Popen([sys.executable, "-m", "oni355.cli.service", "--socket", sock, "--max-requests", "2",
-                            "--no-warm"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                            "--no-warm"], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            text=True)
     try:
         t0 = time.time()
-        while not os.path.exists(sock):
+        while not os.path.exists(tmp_path / sock):
             assert srv.poll() is None, srv.stderr.read()
             assert time.time() - t0 < 120
             time.sleep(0.05)
