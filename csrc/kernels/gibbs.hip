@@ -475,21 +475,37 @@ ONI_API int oni_recount_stream(const int32_t* wsorted, const uint8_t* z_w, int64
 }
 
 // Supported (G, KP) configurations. K ≤ 32: G = 1 (KP = K rounded up to 4).
+static int gibbs_dispatch(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which) {
+  switch (G) {
+    case 1: return oni_gibbs_dispatch_g1(a, KP, init, mode, qpf, s, which);
+    case 2: return oni_gibbs_dispatch_g2(a, KP, init, mode, qpf, s, which);
+    case 4: return oni_gibbs_dispatch_g4(a, KP, init, mode, qpf, s, which);
+    case 8:
+    case 16: return oni_gibbs_dispatch_g8(a, G, KP, init, mode, qpf, s, which);
+    default: break;
+  }
+  return (int)hipErrorInvalidValue;
+}
+
 ONI_API int oni_gibbs_launch(const OniGibbs* a, int G, int KP, int init, int mode, int qpf, hipStream_t s) {
   if (a->nk_rep < 1 || (a->nk_rep & (a->nk_rep - 1))) return (int)hipErrorInvalidValue;
   if (a->K < 1 || a->K > 255 || a->K > a->KS || mode < 0 || mode > 4) return (int)hipErrorInvalidValue;
   if (mode == 2 && !a->chg_mask) return (int)hipErrorInvalidValue;
   if (mode == 3 && (!a->wpos || !a->z_w)) return (int)hipErrorInvalidValue;
   if (mode == 4 && (!a->wpos || !a->zz_w || !a->chg_mask)) return (int)hipErrorInvalidValue;
-  switch (G) {
-    case 1: return oni_gibbs_dispatch_g1(*a, KP, init != 0, mode, qpf, s);
-    case 2: return oni_gibbs_dispatch_g2(*a, KP, init != 0, mode, qpf, s);
-    case 4: return oni_gibbs_dispatch_g4(*a, KP, init != 0, mode, qpf, s);
-    case 8:
-    case 16: return oni_gibbs_dispatch_g8(*a, G, KP, init != 0, mode, qpf, s);
-    default: break;
-  }
-  return (int)hipErrorInvalidValue;
+  return gibbs_dispatch(*a, G, KP, init != 0, mode, qpf, s, nullptr);
+}
+
+// Which kernels would oni_gibbs_launch run for these arguments? Launches nothing and touches no
+// device: of *a only KS, flags and whether exact_guard / tok_zlag are null are read. *first / *twin
+// := the descriptor words (gibbs_sampler.h, Pick) of the first launch and of the guarded generic
+// twin (-1: no twin) -- from the ladder the launch itself goes through.
+ONI_API int oni_gibbs_which(const OniGibbs* a, int G, int KP, int init, int mode, int qpf, int* first, int* twin) {
+  int which[2] = {-1, -1};
+  const int rc = gibbs_dispatch(*a, G, KP, init != 0, mode, qpf, nullptr, which);
+  *first = which[0];
+  *twin = which[1];
+  return rc;
 }
 
 ONI_API int oni_gibbs_sizeof_args() { return (int)sizeof(OniGibbs); }

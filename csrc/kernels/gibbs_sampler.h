@@ -1026,54 +1026,118 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC, 8))
 // Sampler variants (the `qpf` launch argument, oni355.models.gibbs SAMPLERS):
 //   0 = generic k_gibbs (any G; the fallback), 2 = k_gibbs_ldsg (G > 1), 3 = k_gibbs_x1 (G = 1).
 // The specialised kernels need n + α exact in f32 (flags bit 0); otherwise the generic one runs.
-template <int G, int KP>
-int launch_gibbs_one(const OniGibbs& a, bool init, int mode, int qpf, hipStream_t s);
+//
+// select_gibbs is the one selection ladder. It hands the kernel it picks to a visitor as a Pick
+// type: launch_gibbs_one's visitor launches that instantiation, the device-free query
+// (oni_gibbs_which) only reads its descriptor word, so the two cannot disagree.
+enum : int { kFamGeneric = 0, kFamLdsg = 1, kFamX1 = 2 };
+// Descriptor word (decoded by oni355.ops.GibbsKernel): bits 0-1 family, 2-4 MODE, 5 AIR, 6 WPD,
+// 7 ALN, 8 LAG, 9 PKQ, 10 LUT, 11-13 OCC (k_gibbs_ldsg; 0 elsewhere), 14 the kernel returns at once
+// when a guard is present and its flag is 0 (the row-f32 kernels: k_gibbs_x1, k_gibbs_ldsg), 15 the
+// guarded generic twin (flags bit 6: returns when the flag is 1), 16 INIT. The generic kernel has
+// no LAG instantiation: bit 8 tells that it was handed tok_zlag. kPickNone: nothing is launched.
+constexpr int kPickNone = -1;
+constexpr int kPickLag = 1 << 8, kPickGuard = 1 << 14, kPickTwin = 1 << 15;
+template <int FAM, int MODE, bool AIR = false, bool WPD = false, bool ALN = false, bool LAG = false, bool PKQ = false,
+          bool LUT = false, int OCC = 0, bool INIT = false>
+struct Pick {
+  static constexpr int kFam = FAM, kMode = MODE, kOcc = OCC;
+  static constexpr bool kAir = AIR, kWpd = WPD, kAln = ALN, kLag = LAG, kPkq = PKQ, kLut = LUT, kInit = INIT;
+  static constexpr int kCode = FAM | MODE << 2 | (int)AIR << 5 | (int)WPD << 6 | (int)ALN << 7 | (int)LAG << 8 |
+                               (int)PKQ << 9 | (int)LUT << 10 | OCC << 11 | (FAM != kFamGeneric ? kPickGuard : 0) |
+                               (int)INIT << 16;
+};
+// the argument order of the kernel templates (after G / KP)
+template <int MODE, bool INIT = false>
+using PickGeneric = Pick<kFamGeneric, MODE, false, false, false, false, false, false, 0, INIT>;
+template <int MODE, int OCC = 1, bool ALN = false, bool LAG = false>
+using PickLdsg = Pick<kFamLdsg, MODE, true, false, ALN, LAG, false, false, OCC>;
+template <int MODE, bool AIR, bool WPD = false, bool ALN = false, bool LAG = false, bool PKQ = false, bool LUT = false>
+using PickX1 = Pick<kFamX1, MODE, AIR, WPD, ALN, LAG, PKQ, LUT>;
 
-// With a device exactness guard (a.exact_guard) the row-f32 kernel and the generic kernel are both
-// launched; each reads the flag and all but one return at once -- a per-sweep choice that graph
-// replays keep making on the device (the same draws either way: every variant replays the oracle).
-template <int G, int KP>
-int launch_gibbs(const OniGibbs& a, bool init, int mode, int qpf, hipStream_t s) {
-  const int rc = launch_gibbs_one<G, KP>(a, init, mode, qpf, s);
-  if (rc != 0 || init || a.exact_guard == nullptr || !(a.flags & 1) || (qpf != 2 && qpf != 3)) return rc;
-  OniGibbs b = a;
-  b.flags = (b.flags & ~1) | 64;  // no row-f32 kernel: the generic one, guarded
-  return launch_gibbs_one<G, KP>(b, init, mode, 0, s);
+template <int G, int KP, class P>
+void launch_pick(P, const OniGibbs& a, unsigned grid, hipStream_t s) {
+  if constexpr (P::kFam == kFamX1) {
+    k_gibbs_x1<KP, P::kMode, P::kAir, P::kWpd, P::kAln, P::kLag, P::kPkq, P::kLut><<<grid, kBlock, 0, s>>>(a);
+  } else if constexpr (P::kFam == kFamLdsg) {
+    k_gibbs_ldsg<G, KP, P::kMode, P::kOcc, P::kAln, P::kLag><<<grid, kBlock, 0, s>>>(a);
+  } else {
+    k_gibbs<G, KP, P::kInit, P::kMode><<<grid, kBlock, 0, s>>>(a);
+  }
 }
 
+template <int G, int KP, class F>
+int select_gibbs(const OniGibbs& a, bool init, int mode, int qpf, F&& f);
+
+// One launch (dry: none): *code := the descriptor word of the kernel the ladder picks.
 template <int G, int KP>
-int launch_gibbs_one(const OniGibbs& a, bool init, int mode, int qpf, hipStream_t s) {
+int launch_gibbs_one(const OniGibbs& a, bool init, int mode, int qpf, hipStream_t s, bool dry, int* code) {
+  *code = kPickNone;
   if (a.KS != G * KP || mode < 0 || mode > 4) return (int)hipErrorInvalidValue;
   const unsigned grid = (unsigned)((a.n_slices + kWavesPerBlock - 1) / kWavesPerBlock);
-  if (grid == 0) return 0;
+  if (dry || grid == 0) {
+    *code = select_gibbs<G, KP>(a, init, mode, qpf, [](auto p) { return decltype(p)::kCode; });
+  } else {
+    if (!init && a.qfix == nullptr) return (int)hipErrorInvalidValue;
+    *code = select_gibbs<G, KP>(a, init, mode, qpf, [&](auto p) {
+      launch_pick<G, KP>(p, a, grid, s);
+      return decltype(p)::kCode;
+    });
+  }
+  if ((*code & 3) == kFamGeneric && !init) {
+    *code |= (a.tok_zlag != nullptr ? kPickLag : 0) | ((a.flags & 64) ? kPickTwin : 0);
+  }
+  return (dry || grid == 0) ? 0 : (int)hipGetLastError();
+}
+
+// With a device exactness guard (a.exact_guard) a row-f32 kernel and the generic kernel are both
+// launched; each reads the flag and one of them returns at once -- a per-sweep choice that graph
+// replays keep making on the device (the same draws either way: every variant replays the oracle).
+// The twin follows only a first pick that returns at flag 0: where the ladder already picked the
+// generic kernel (e.g. tok_zlag outside recount / wdelta or with unaligned one-lane chunks) that
+// kernel runs alone and unguarded -- it is exact for any counts -- so exactly one sampler sweeps
+// the tokens for either flag value.
+// which (optional, [2]): the descriptor words of the first launch and of the twin (kPickNone:
+// no twin) are written there and nothing is launched.
+template <int G, int KP>
+int launch_gibbs(const OniGibbs& a, bool init, int mode, int qpf, hipStream_t s, int* which) {
+  const bool dry = which != nullptr;
+  int first = kPickNone, twin = kPickNone;
+  int rc = launch_gibbs_one<G, KP>(a, init, mode, qpf, s, dry, &first);
+  if (rc == 0 && !init && a.exact_guard != nullptr && first != kPickNone && (first & kPickGuard)) {
+    OniGibbs b = a;
+    b.flags = (b.flags & ~1) | 64;  // no row-f32 kernel: the generic one, guarded
+    rc = launch_gibbs_one<G, KP>(b, init, mode, 0, s, dry, &twin);
+  }
+  if (dry) which[0] = first, which[1] = twin;
+  return rc;
+}
+
+template <int G, int KP, class F>
+int select_gibbs(const OniGibbs& a, bool init, int mode, int qpf, F&& f) {
   if (init) {
     // mode 1: n_wk by per-token atomics; mode 0: no n_wk bookkeeping, the caller rebuilds it with
     // the word-sorted recount
-    if (mode == 0) k_gibbs<G, KP, true, 0><<<grid, kBlock, 0, s>>>(a);
-    else k_gibbs<G, KP, true, 1><<<grid, kBlock, 0, s>>>(a);
-    return (int)hipGetLastError();
+    if (mode == 0) return f(PickGeneric<0, true>{});
+    return f(PickGeneric<1, true>{});
   }
-  if (a.qfix == nullptr) return (int)hipErrorInvalidValue;
   const bool air = (a.flags & 1) != 0;
   if (a.tok_zlag != nullptr) {
     // lagged word side: the specialised kernels on the default paths (aligned chunks, recount /
     // wdelta), the generic kernel (which reads tok_zlag at run time) for anything else
     if constexpr (G == 1) {
       if (qpf == 3 && KP <= 32 && air && (a.flags & 16) && !(a.flags & 2) && (mode == 0 || mode == 4)) {
-        if (mode == 0) k_gibbs_x1<KP, 0, true, false, true, true><<<grid, kBlock, 0, s>>>(a);
-        else k_gibbs_x1<KP, 4, true, false, true, true><<<grid, kBlock, 0, s>>>(a);
-        return (int)hipGetLastError();
+        if (mode == 0) return f(PickX1<0, true, false, true, true>{});
+        return f(PickX1<4, true, false, true, true>{});
       }
     } else {
       if (qpf == 2 && air && (a.flags & 16) && (G == 2 || G == 4) && (mode == 0 || mode == 4)) {
-        if (mode == 0) k_gibbs_ldsg<G, KP, 0, 1, true, true><<<grid, kBlock, 0, s>>>(a);
-        else k_gibbs_ldsg<G, KP, 4, 1, true, true><<<grid, kBlock, 0, s>>>(a);
-        return (int)hipGetLastError();
+        if (mode == 0) return f(PickLdsg<0, 1, true, true>{});
+        return f(PickLdsg<4, 1, true, true>{});
       }
       if (qpf == 2 && air && (mode == 0 || mode == 4)) {
-        if (mode == 0) k_gibbs_ldsg<G, KP, 0, 1, false, true><<<grid, kBlock, 0, s>>>(a);
-        else k_gibbs_ldsg<G, KP, 4, 1, false, true><<<grid, kBlock, 0, s>>>(a);
-        return (int)hipGetLastError();
+        if (mode == 0) return f(PickLdsg<0, 1, false, true>{});
+        return f(PickLdsg<4, 1, false, true>{});
       }
     }
   } else if constexpr (G == 1) {
@@ -1082,86 +1146,79 @@ int launch_gibbs_one(const OniGibbs& a, bool init, int mode, int qpf, hipStream_
       // flags bit 5 (ONI_SAMPLER_AB & 4): A/B of the packed q' (v_pk_fma_f32) against the scalar
       // one -- 30 fewer VALU per two steps, 3.5 % slower per sweep (profiles/r6/packed_fp32/)
       if (a.flags & 32) {
-        if (mode == 0) k_gibbs_x1<KP, 0, true, false, true, false, true><<<grid, kBlock, 0, s>>>(a);
-        else k_gibbs_x1<KP, 4, true, false, true, false, true><<<grid, kBlock, 0, s>>>(a);
-        return (int)hipGetLastError();
+        if (mode == 0) return f(PickX1<0, true, false, true, false, true>{});
+        return f(PickX1<4, true, false, true, false, true>{});
       }
       if (a.flags & 128) {  // A/B (ONI_SAMPLER_AB & 8): the ±1 count update by per-topic bfe + cvt (round 5)
-        if (mode == 0) k_gibbs_x1<KP, 0, true, false, true><<<grid, kBlock, 0, s>>>(a);
-        else k_gibbs_x1<KP, 4, true, false, true><<<grid, kBlock, 0, s>>>(a);
-        return (int)hipGetLastError();
+        if (mode == 0) return f(PickX1<0, true, false, true>{});
+        return f(PickX1<4, true, false, true>{});
       }
       // default: the ±1 count update through the LDS table of float pairs (4 % faster per sweep,
       // profiles/r6/count_lut/)
-      if (mode == 0) k_gibbs_x1<KP, 0, true, false, true, false, false, true><<<grid, kBlock, 0, s>>>(a);
-      else k_gibbs_x1<KP, 4, true, false, true, false, false, true><<<grid, kBlock, 0, s>>>(a);
-      return (int)hipGetLastError();
+      if (mode == 0) return f(PickX1<0, true, false, true, false, false, true>{});
+      return f(PickX1<4, true, false, true, false, false, true>{});
     }
     if (qpf == 3 && KP <= 32) {
       if ((a.flags & 2) && (mode == 3 || mode == 4)) {  // A/B: word-sorted slots loaded on change
-        if (air && mode == 4) k_gibbs_x1<KP, 4, true, true><<<grid, kBlock, 0, s>>>(a);
-        else if (air) k_gibbs_x1<KP, 3, true, true><<<grid, kBlock, 0, s>>>(a);
-        else if (mode == 4) k_gibbs_x1<KP, 4, false, true><<<grid, kBlock, 0, s>>>(a);
-        else k_gibbs_x1<KP, 3, false, true><<<grid, kBlock, 0, s>>>(a);
-        return (int)hipGetLastError();
+        if (air && mode == 4) return f(PickX1<4, true, true>{});
+        if (air) return f(PickX1<3, true, true>{});
+        if (mode == 4) return f(PickX1<4, false, true>{});
+        return f(PickX1<3, false, true>{});
       }
       if (air) {
         switch (mode) {
-          case 0: k_gibbs_x1<KP, 0, true><<<grid, kBlock, 0, s>>>(a); break;
-          case 1: k_gibbs_x1<KP, 1, true><<<grid, kBlock, 0, s>>>(a); break;
-          case 2: k_gibbs_x1<KP, 2, true><<<grid, kBlock, 0, s>>>(a); break;
-          case 3: k_gibbs_x1<KP, 3, true><<<grid, kBlock, 0, s>>>(a); break;
-          default: k_gibbs_x1<KP, 4, true><<<grid, kBlock, 0, s>>>(a); break;
+          case 0: return f(PickX1<0, true>{});
+          case 1: return f(PickX1<1, true>{});
+          case 2: return f(PickX1<2, true>{});
+          case 3: return f(PickX1<3, true>{});
+          default: return f(PickX1<4, true>{});
         }
       } else {
         switch (mode) {
-          case 0: k_gibbs_x1<KP, 0, false><<<grid, kBlock, 0, s>>>(a); break;
-          case 1: k_gibbs_x1<KP, 1, false><<<grid, kBlock, 0, s>>>(a); break;
-          case 2: k_gibbs_x1<KP, 2, false><<<grid, kBlock, 0, s>>>(a); break;
-          case 3: k_gibbs_x1<KP, 3, false><<<grid, kBlock, 0, s>>>(a); break;
-          default: k_gibbs_x1<KP, 4, false><<<grid, kBlock, 0, s>>>(a); break;
+          case 0: return f(PickX1<0, false>{});
+          case 1: return f(PickX1<1, false>{});
+          case 2: return f(PickX1<2, false>{});
+          case 3: return f(PickX1<3, false>{});
+          default: return f(PickX1<4, false>{});
         }
       }
-      return (int)hipGetLastError();
     }
   } else {
     if (qpf == 2 && air && (a.flags & 4) && (mode == 0 || mode == 4)) {  // A/B: 4-wave register budget
-      if (mode == 0) k_gibbs_ldsg<G, KP, 0, 4><<<grid, kBlock, 0, s>>>(a);
-      else k_gibbs_ldsg<G, KP, 4, 4><<<grid, kBlock, 0, s>>>(a);
-      return (int)hipGetLastError();
+      if (mode == 0) return f(PickLdsg<0, 4>{});
+      return f(PickLdsg<4, 4>{});
     }
     if (qpf == 2 && air && (a.flags & 16) && (G == 2 || G == 4) && (mode == 0 || mode == 4)) {
       // every chunk starts at a multiple of 4 tokens: uniform Philox word, DPP exchange
-      if (mode == 0) k_gibbs_ldsg<G, KP, 0, 1, true><<<grid, kBlock, 0, s>>>(a);
-      else k_gibbs_ldsg<G, KP, 4, 1, true><<<grid, kBlock, 0, s>>>(a);
-      return (int)hipGetLastError();
+      if (mode == 0) return f(PickLdsg<0, 1, true>{});
+      return f(PickLdsg<4, 1, true>{});
     }
     if (qpf == 2 && air) {
       switch (mode) {
-        case 0: k_gibbs_ldsg<G, KP, 0><<<grid, kBlock, 0, s>>>(a); break;
-        case 1: k_gibbs_ldsg<G, KP, 1><<<grid, kBlock, 0, s>>>(a); break;
-        case 2: k_gibbs_ldsg<G, KP, 2><<<grid, kBlock, 0, s>>>(a); break;
-        case 3: k_gibbs_ldsg<G, KP, 3><<<grid, kBlock, 0, s>>>(a); break;
-        default: k_gibbs_ldsg<G, KP, 4><<<grid, kBlock, 0, s>>>(a); break;
+        case 0: return f(PickLdsg<0>{});
+        case 1: return f(PickLdsg<1>{});
+        case 2: return f(PickLdsg<2>{});
+        case 3: return f(PickLdsg<3>{});
+        default: return f(PickLdsg<4>{});
       }
-      return (int)hipGetLastError();
     }
   }
   switch (mode) {
-    case 0: k_gibbs<G, KP, false, 0><<<grid, kBlock, 0, s>>>(a); break;
-    case 1: k_gibbs<G, KP, false, 1><<<grid, kBlock, 0, s>>>(a); break;
-    case 2: k_gibbs<G, KP, false, 2><<<grid, kBlock, 0, s>>>(a); break;
-    case 3: k_gibbs<G, KP, false, 3><<<grid, kBlock, 0, s>>>(a); break;
-    default: k_gibbs<G, KP, false, 4><<<grid, kBlock, 0, s>>>(a); break;
+    case 0: return f(PickGeneric<0>{});
+    case 1: return f(PickGeneric<1>{});
+    case 2: return f(PickGeneric<2>{});
+    case 3: return f(PickGeneric<3>{});
+    default: return f(PickGeneric<4>{});
   }
-  return (int)hipGetLastError();
 }
 
 }  // namespace
 
 // Per-unit-width dispatchers (gibbs_g1.hip, gibbs_g2.hip, gibbs_g4.hip, gibbs_g8.hip): launch
-// launch_gibbs<G, KP> for a supported KP; hipErrorInvalidValue otherwise.
-int oni_gibbs_dispatch_g1(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s);
-int oni_gibbs_dispatch_g2(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s);
-int oni_gibbs_dispatch_g4(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s);
-int oni_gibbs_dispatch_g8(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s);
+// launch_gibbs<G, KP> for a supported KP; hipErrorInvalidValue otherwise. which != nullptr: the
+// query (no launch, see launch_gibbs).
+int oni_gibbs_dispatch_g1(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
+int oni_gibbs_dispatch_g2(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
+int oni_gibbs_dispatch_g4(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
+int oni_gibbs_dispatch_g8(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s,
+                          int* which);

@@ -743,6 +743,16 @@ class GibbsLDA:
             self._zw_synced = mode == 3
             self._last_inplace = inplace
 
+    def sweep_kernels(self, mode: int | None = None, lag: bool | None = None):
+        """(first, twin): the ops.GibbsKernel picks of a device sweep of this model in count mode
+        ``mode`` (default: the next sweep's), with the lagged word side or not (default: as now) --
+        what :meth:`_one_sweep` hands to ops.gibbs_pass, asked of the launcher's own ladder
+        (ops.gibbs_which: nothing is launched). Dense samplers only."""
+        if mode is None:
+            mode = self._sweep_mode(self.sweeps_done + 1)
+        return ops.gibbs_which(self.G, self.KP, mode, self.qpf, alpha_in_row=self._air, pos_aligned=self._pos_aligned,
+                               lag=self._lag_live if lag is None else lag, guard=self._guard is not None)
+
     def _clean_heads(self) -> None:
         """Zero both Δ heads before a sweep that writes one after in-place sweeps: an in-place apply
         neither reads nor zeroes them, so the head a non-in-place sweep left behind is still there

@@ -12,6 +12,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -21,7 +22,7 @@ from . import _lib
 
 __all__ = [
     "f32_keys", "i64_keys", "quantile_cuts", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
-    "sell_perm_z", "gibbs_pass", "gibbs_apply", "mh_tables", "SAMPLER_MH", "copy_rows", "score", "select_below", "choose_tiling",
+    "sell_perm_z", "gibbs_pass", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "copy_rows", "score", "select_below", "choose_tiling",
 ]
 
 
@@ -377,6 +378,11 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
     ``sampler`` (kernel variant; every variant draws the same topics bit for bit): 0 = generic
     k_gibbs, 2 = k_gibbs_ldsg (G > 1), 3 = k_gibbs_x1 (G = 1); the specialised kernels need
     ``alpha_in_row`` (n + α exact in f32 for every count of the corpus), else the generic one runs.
+    With ``st["exact_guard"]`` a specialised kernel returns at once on a sweep whose flag is 0 and
+    a guarded generic twin, launched behind it, samples instead; the twin is launched only behind
+    a specialised first pick -- where the ladder itself picks the generic kernel (``tok_zlag``
+    outside recount / wdelta, or with unaligned one-lane chunks) that kernel runs alone, so one
+    sampler sweeps the tokens whatever the flag says. :func:`gibbs_which` names the picks.
     4 = k_gibbs_mh, the Metropolis-Hastings sampler (one-lane units, chunks ≤ 127 tokens; NOT the
     same draws: its own oracle spec.gibbs_pass_mh) which also needs the word proposal
     (``st["walias"]`` + ``st["wsum"]``, or ``st["wcdf"]``), ``st["dalias"]``, ``st["mh_g"]``
@@ -467,14 +473,11 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
     # (k_gibbs_x1), bit 1 = 4-wave register budget (k_gibbs_ldsg)
     # pos_aligned: every chunk starts at a multiple of 4 tokens (chunk length % 4 == 0), so the
     # one-lane sampler picks its Philox word by the uniform step index (bit 4)
-    ab = int(os.environ.get("ONI_SAMPLER_AB", "0"))
     # bit 2 of ONI_SAMPLER_AB (flags bit 5): k_gibbs_x1's q' by v_pk_fma_f32 on topic pairs (A/B: loses);
     # bit 3 (flags bit 7): its ±1 count update by per-topic bfe + cvt instead of the LDS table (A/B);
     # bit 5 (flags bit 9): k_gibbs_mh's round-5 level-1 word CDF gathers (one lane per row, words two
     # tokens ahead) instead of four lanes per row a step ahead (A/B)
-    a.flags = ((1 if alpha_in_row else 0) | (ab & 3) << 1 | (8 if (init and word_init) else 0)
-               | (16 if pos_aligned else 0) | (32 if ab & 4 else 0) | (128 if ab & 8 else 0)
-               | (512 if ab & 32 else 0))
+    a.flags = _gibbs_flags(alpha_in_row, init and word_init, pos_aligned)
     if sampler == SAMPLER_MH:
         if G != 1:
             raise ValueError("the MH sampler runs one-lane units")
@@ -498,6 +501,62 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
         return
     _lib.check(_lib.lib().oni_gibbs_launch(C.byref(a), G, KP, 1 if init else 0, int(mode), int(sampler),
                                            _lib.stream()), "oni_gibbs_launch")
+
+
+def _gibbs_flags(alpha_in_row: bool, word_init: bool, pos_aligned: bool) -> int:
+    """OniGibbs.flags of a pass (the kernel A/B bits come from ONI_SAMPLER_AB)."""
+    ab = int(os.environ.get("ONI_SAMPLER_AB", "0"))
+    return ((1 if alpha_in_row else 0) | (ab & 3) << 1 | (8 if word_init else 0) | (16 if pos_aligned else 0)
+            | (32 if ab & 4 else 0) | (128 if ab & 8 else 0) | (512 if ab & 32 else 0))
+
+
+class GibbsKernel(NamedTuple):
+    """One pick of the dense samplers' selection ladder (select_gibbs, csrc/kernels/gibbs_sampler.h):
+    the kernel family and its template arguments. ``lag`` of the generic kernel (which has no LAG
+    instantiation) tells that it is handed tok_zlag. ``guard``: a row-f32 kernel, which returns at
+    once on a sweep whose exactness flag is 0 when a guard is present; ``twin``: the guarded
+    generic kernel launched behind such a kernel (returns when the flag is 1)."""
+
+    family: str  # "generic" (k_gibbs) | "ldsg" (k_gibbs_ldsg) | "x1" (k_gibbs_x1)
+    mode: int
+    air: bool
+    wpd: bool
+    aln: bool
+    lag: bool
+    pkq: bool
+    lut: bool
+    occ: int  # k_gibbs_ldsg's waves-per-EU budget (0 for the other families)
+    guard: bool
+    twin: bool
+    init: bool
+
+    @classmethod
+    def decode(cls, code: int) -> "GibbsKernel | None":
+        if code < 0:
+            return None
+        bit = lambda i: bool(code >> i & 1)  # noqa: E731
+        return cls(("generic", "ldsg", "x1")[code & 3], code >> 2 & 7, bit(5), bit(6), bit(7), bit(8), bit(9), bit(10),
+                   code >> 11 & 7, bit(14), bit(15), bit(16))
+
+
+def gibbs_which(G: int, KP: int, mode: int, sampler: int, *, alpha_in_row: bool = False, pos_aligned: bool = False,
+                lag: bool = False, guard: bool = False, init: bool = False) -> tuple[GibbsKernel, GibbsKernel | None]:
+    """The kernels :func:`gibbs_pass` launches on the device for these arguments (and the current
+    ONI_SAMPLER_AB): the first launch and the guarded generic twin (None: no twin). ``lag`` /
+    ``guard``: ``st`` carries ``tok_zlag`` / ``exact_guard``. Asks the launcher's own selection
+    ladder (oni_gibbs_which); launches nothing and needs no device."""
+    if sampler == SAMPLER_MH:
+        raise ValueError("gibbs_which describes the dense samplers (k_gibbs_mh has its own launcher)")
+    a = _lib.OniGibbs()
+    a.KS = G * KP
+    a.flags = _gibbs_flags(alpha_in_row, False, pos_aligned)
+    if not init:  # like gibbs_pass: only whether the pointers are null is read
+        a.exact_guard = 1 if guard else None
+        a.tok_zlag = 1 if lag else None
+    first, twin = C.c_int(-1), C.c_int(-1)
+    _lib.check(_lib.lib().oni_gibbs_which(C.byref(a), G, KP, 1 if init else 0, int(mode), int(sampler),
+                                          C.byref(first), C.byref(twin)), "oni_gibbs_which")
+    return GibbsKernel.decode(first.value), GibbsKernel.decode(twin.value)
 
 
 def mh_tables(q: torch.Tensor, nk: torch.Tensor, ndk_src: torch.Tensor, long_rows: torch.Tensor, K: int,

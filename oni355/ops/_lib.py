@@ -57,6 +57,8 @@ _SIGS = {
     "oni_sell_fill": [vp, vp, vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp],
     "oni_sell_perm_z": [vp, vp, vp, i64, C.c_int, vp, vp, vp, vp, C.c_int, vp],
     "oni_gibbs_launch": [C.POINTER(OniGibbs), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp],
+    "oni_gibbs_which": [C.POINTER(OniGibbs), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                        C.POINTER(C.c_int)],
     "oni_gibbs_sizeof_args": [],
     "oni_exact_guard": [vp, vp, i64, C.c_int, C.c_int, C.c_int32, vp, vp],
     "oni_gibbs_mh_launch": [C.POINTER(OniMH), C.c_int, C.c_int, vp],

@@ -102,6 +102,8 @@ def test_gibbs_bitwise_vs_oracle(gpu, K, mode):
     exact = K not in (7, 12)  # α = 50/K exact in f32 (and below 2^24 documents) selects the fast kernels
     if sampler == "dense":
         assert mg.qpf == ((3 if G == 1 else 2) if exact else 0), (K, mg.qpf)
+    first, twin = mg.sweep_kernels()  # the launcher's own pick: the kernel the docstring names, and no twin
+    assert (first.family, first.mode, twin) == ({0: "generic", 2: "ldsg", 3: "x1"}[mg.qpf], mg.mode, None)
     mc = GibbsLDA(cc, GibbsConfig(K=K, seed=1234, use_graph=False, count_mode="atomic", sampler="dense"))
     if mode.startswith("wdelta"):
         assert mg.mode == 4
