@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Interleaved A/B of fold-in scoring against training on ONE generated flow day (one process):
+
+  train    run_flow at the bench.py default shape (the day trains its own model)
+  infer    score_flow against a model trained once (every sweep of a single-chunk document in one
+           launch)
+  unfused  score_flow with sweep fusion off (one launch per sweep)
+
+  python bench/foldin.py --flows 12500000 --topics 20 --rounds 3 --out profiles/foldin/bench.json
+
+Prints one JSON line per day and a summary: median / min ms per day, ms per fold-in sweep (the
+``foldin`` stage over the fold-in sweeps) and the run-to-run spread (max − min) of every variant.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--flows", type=int, default=12_500_000)
+    ap.add_argument("--topics", type=int, default=20)
+    ap.add_argument("--sweeps", type=int, default=200, help="training sweeps")
+    ap.add_argument("--infer-sweeps", type=int, default=30)
+    ap.add_argument("--avg-last", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    import torch
+
+    from oni355.models.saved import SavedModel
+    from oni355.pipeline.flow import run_flow, score_flow
+    from oni355.synth.flow import generate_flows
+
+    dev = torch.device(a.device)
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    day = generate_flows(a.flows, seed=a.seed, n_hosts=max(64, a.flows // 25))
+    print(f"generated {a.flows} flows in {time.perf_counter() - t0:.1f} s", flush=True)
+    kw = dict(tol=1.0, maxresults=3000, device=dev)
+    # the model is trained once (this untimed day is also the warm-up of the training variant)
+    first = run_flow(day.cols, K=a.topics, sweeps=a.sweeps, **kw)
+    model = SavedModel.from_run(first.lda, first.cuts, "flow", {"day": "bench"})
+    top_train = set(first.rows.tolist())
+    del first
+    ikw = dict(sweeps=a.infer_sweeps, avg_last=a.avg_last, **kw)
+    score_flow(day.cols, model, **ikw)  # untimed warm-up of the fold-in variants
+    variants = {"train": lambda: run_flow(day.cols, K=a.topics, sweeps=a.sweeps, **kw),
+                "infer": lambda: score_flow(day.cols, model, **ikw),
+                "unfused": lambda: score_flow(day.cols, model, fuse=False, **ikw)}
+    days = {n: [] for n in variants}
+    for r in range(a.rounds):
+        for name, fn in variants.items():
+            sync()
+            ts = time.perf_counter()
+            res = fn()
+            sync()
+            wall = time.perf_counter() - ts
+            t = res.timings
+            line = {"variant": name, "round": r, "day_ms": round(wall * 1e3, 2)}
+            if name == "train":
+                line["ms_per_sweep"] = round(t.get("train_dev_s", t.get("train_s", 0.0)) / a.sweeps * 1e3, 4)
+            else:
+                line["ms_per_sweep"] = round(t.get("foldin_dev_s", t.get("foldin_s", 0.0)) / max(a.infer_sweeps, 1) * 1e3, 4)
+                line["launches"] = res.stats["foldin_launches"]
+                line["overlap_with_training"] = round(len(top_train & set(res.rows.tolist())) / max(len(top_train), 1), 4)
+            days[name].append(line)
+            print(json.dumps(line), flush=True)
+            del res
+
+    def summ(v):
+        d, s = [x["day_ms"] for x in v], [x["ms_per_sweep"] for x in v]
+        return {"day_ms_median": statistics.median(d), "day_ms_min": min(d), "day_ms_spread": round(max(d) - min(d), 2),
+                "ms_per_sweep_median": statistics.median(s), "ms_per_sweep_min": min(s),
+                "ms_per_sweep_spread": round(max(s) - min(s), 4)}
+    summary = {n: summ(v) for n, v in days.items()}
+    out = {"flows": a.flows, "topics": a.topics, "train_sweeps": a.sweeps, "infer_sweeps": a.infer_sweeps,
+           "avg_last": a.avg_last, "rounds": a.rounds, "summary": summary, "days": days}
+    print(json.dumps({"summary": summary}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -52,6 +52,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eval-every", type=int, default=None)
     ap.add_argument("--ldac-out", default=None, help="write lda-c files (final.beta/gamma/other, likelihood.dat)")
     ap.add_argument("--ldac-lag", type=int, default=0, help="also write lda-c NNN.* snapshots every N sweeps")
+    ap.add_argument("--save-model", metavar="DIR", default=None,
+                    help="after training, write DIR/<source>_model.npz (the model --model scores against)")
+    ap.add_argument("--model", metavar="FILE", default=None,
+                    help="score the day's events against this saved model (fold-in inference) instead of training")
+    ap.add_argument("--infer-sweeps", type=int, default=30, help="--model: fold-in sweeps")
+    ap.add_argument("--infer-avg-last", type=int, default=10, help="--model: sweeps averaged into theta")
     ap.add_argument("--burnin", type=int, default=None, help="sweeps before the likelihood trace / snapshots")
     ap.add_argument("--max-restarts", type=int, default=0,
                     help="supervise the run: after a failure (crash, watchdog exit, numerical fault) start a "
@@ -234,6 +240,20 @@ def main(argv=None) -> int:
                       CKPT_EVERY=a.ckpt_every, TOP_DOMAINS=a.top_domains, TOL=a.tol, MAXRESULTS=a.maxresults,
                       ALPHA=a.alpha, BURNIN=a.burnin)
     inside = os.environ.get("ONI_MLD_INSIDE") == "1"
+    gpus_asked = a.gpus if a.gpus is not None else cfg.PROCESS_COUNT
+    if a.model or a.save_model:
+        opt = "--model" if a.model else "--save-model"
+        if a.source != "flow":
+            raise SystemExit(f"oni-ml: {opt} supports flow only: {a.source} words depend on per-day dictionaries "
+                             "(saved-model scoring for dns / proxy is a follow-up)")
+        if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
+    if a.model:
+        for flag, val in (("--ckpt-dir", a.ckpt_dir), ("--ldac-out", a.ldac_out), ("--save-model", a.save_model)):
+            if val:
+                raise SystemExit(f"oni-ml: --model scores against a saved model and trains nothing; {flag} does not apply")
+        if not os.path.isfile(a.model):
+            raise SystemExit(f"oni-ml: --model {a.model}: no such file")
     if a.max_restarts > 0 and os.environ.get("ONI_SUPERVISED") != "1":
         if inside:
             # the supervisor's children would write to the service's stdout, not the client's
@@ -261,6 +281,8 @@ def main(argv=None) -> int:
     log = (lambda m: None) if (a.quiet or rank) else (lambda m: print(f"[oni-ml] {m}", file=sys.stderr, flush=True))
     from ..pipeline.daily import parse_dates
     dates = parse_dates(a.date)
+    if (a.model or a.save_model) and (len(dates) > 1 or a.follow):
+        raise SystemExit("oni-ml: --model / --save-model apply to single-day runs")
     if len(dates) > 1 or a.follow:
         return _main_days(a, cfg, comm, device, dates, log)
     t0 = time.perf_counter()
@@ -288,9 +310,23 @@ def main(argv=None) -> int:
     if a.ldac_out and a.ldac_lag > 0:
         common_kw.update(ldac_dir=os.path.join(a.ldac_out, f"rank{rank}") if world > 1 else a.ldac_out,
                          ldac_lag=a.ldac_lag)
-    if a.source == "flow":
+    if a.model:
+        from ..models.saved import SavedModel
+        from ..pipeline.flow import score_flow
+        model = SavedModel.load(a.model)
+        log(f"model {a.model}: K={model.K}, V={model.V}, trained {model.provenance}")
+        res = score_flow(cols, model, tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps,
+                         avg_last=a.infer_avg_last, seed=cfg.SEED, device=device, comm=comm, feedback=fb,
+                         chunk_len=cfg.CHUNK_LEN, row_offset=row_off, log=log)
+    elif a.source == "flow":
         from ..pipeline.flow import run_flow
         res = run_flow(cols, **common_kw)
+        if a.save_model:
+            from ..models.saved import SavedModel
+            os.makedirs(a.save_model, exist_ok=True)
+            mp = SavedModel.from_run(res.lda, res.cuts, "flow", {"day": a.date}).save(
+                os.path.join(a.save_model, "flow_model.npz"))
+            log(f"saved model -> {mp}")
     elif a.source == "dns":
         from ..pipeline.dns import run_dns
         res = run_dns(cols, top_domains=top, user_domain=cfg.USER_DOMAIN, **common_kw)

@@ -22,7 +22,7 @@ from . import _lib
 
 __all__ = [
     "f32_keys", "i64_keys", "quantile_cuts", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
-    "sell_perm_z", "gibbs_pass", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "copy_rows", "score", "select_below", "choose_tiling",
+    "sell_perm_z", "gibbs_pass", "foldin_pass", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "copy_rows", "score", "select_below", "choose_tiling",
 ]
 
 
@@ -501,6 +501,69 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
         return
     _lib.check(_lib.lib().oni_gibbs_launch(C.byref(a), G, KP, 1 if init else 0, int(mode), int(sampler),
                                            _lib.stream()), "oni_gibbs_launch")
+
+
+def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init: bool, sweep_lo: int,
+                n_sweeps: int, avg_from: int, chunk_len: torch.Tensor, select: int = 0) -> None:
+    """Fold-in against a frozen word table (k_foldin, csrc/kernels/foldin.hip): the init pass
+    (``init``) or sweeps ``sweep_lo`` .. ``sweep_lo + n_sweeps − 1`` in ONE launch.
+
+    ``st``: tok_word, tok_z, slice_off, slice_len, chunk_doc, chunk_pos0, chunk_key, chunk_multi,
+    ndk_src, ndk_dst (int32 [D, KS]), ndk_sum (int32 [D, KS]) and ``phi`` (f32 [V + 1, KS], row V =
+    the out-of-vocabulary row, columns ≥ K zero). ``select``: 0 every chunk, 1 the chunks of
+    single-chunk documents, 2 the chunks of multi-chunk documents. A single-chunk document reads
+    its ``ndk_src`` row once, runs all the sweeps, stores the row to ``ndk_dst`` (which may be
+    ``ndk_src``) and adds the rows after the sweeps ≥ ``avg_from`` into ``ndk_sum``. A multi-chunk
+    document's chunks add their Δ into ``ndk_dst`` (a pre-copied row of another buffer), one sweep
+    a launch -- ``n_sweeps`` > 1 therefore needs ``select`` 1 -- and their window sums are the
+    caller's. CPU tensors run the oracle (:func:`oni355.ref.foldin_spec.foldin_pass`)."""
+    from ..ref import foldin_spec
+    if select not in (0, 1, 2):
+        raise ValueError("select must be 0 (all), 1 (single-chunk docs) or 2 (multi-chunk docs)")
+    if init:
+        sweep_lo, n_sweeps = 0, 1
+    elif n_sweeps < 1 or sweep_lo < 1:
+        raise ValueError("sweeps are numbered from 1 and a launch runs at least one")
+    elif n_sweeps > 1 and select != 1:
+        raise ValueError("only single-chunk documents run several sweeps in one launch (select=1)")
+    KS = G * KP
+    if st["phi"].shape[-1] != KS or st["ndk_src"].shape[-1] != KS or st["ndk_dst"].shape[-1] != KS:
+        raise ValueError("phi / ndk row width must equal G*KP")
+    if st["ndk_sum"].shape != st["ndk_dst"].shape or st["ndk_sum"].dtype != torch.int32:
+        raise ValueError("ndk_sum must be an int32 table of the doc rows' shape")
+    in_place = st["ndk_src"].data_ptr() == st["ndk_dst"].data_ptr()
+    if select != 1 and not init and in_place and bool(st["chunk_multi"].any()):
+        raise ValueError("multi-chunk documents add their deltas into a pre-copied row of another buffer")
+    s0, s1 = spec.split_seed(seed)
+    if not _is_dev(st["tok_word"]):
+        npst = {k: (v.numpy().view(np.uint32) if k in ("tok_word", "chunk_key") else v.numpy())
+                for k, v in st.items() if isinstance(v, torch.Tensor)}
+        cl = chunk_len.numpy()
+        if init:
+            foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, True, 0, cl, select)
+            return
+        docs = npst["chunk_doc"][(npst["chunk_doc"] >= 0) & (npst["chunk_multi"] == 0)]
+        for sweep in range(sweep_lo, sweep_lo + n_sweeps):
+            foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, False, sweep, cl, select)
+            npst["ndk_src"] = npst["ndk_dst"]  # one launch: the rows stay with their unit
+            if sweep >= avg_from and select != 2:
+                npst["ndk_sum"][docs] += npst["ndk_dst"][docs]
+        return
+    n_slices = st["slice_len"].numel()
+    if st["chunk_doc"].numel() != n_slices * (64 // G):
+        raise ValueError("chunk table must hold S chunks per slice")
+    L = _lib.lib()
+    if not hasattr(L, "oni_foldin_launch"):
+        raise RuntimeError("liboni_hip.so has no fold-in kernel (oni_foldin_launch): rebuild with `python tools/build.py`")
+    if L.oni_foldin_sizeof_args() != C.sizeof(_lib.OniFoldin):
+        raise RuntimeError("OniFoldin ABI mismatch between Python and liboni_hip.so; rebuild")
+    a = _lib.OniFoldin()
+    for name in ("tok_word", "tok_z", "slice_off", "slice_len", "chunk_doc", "chunk_pos0", "chunk_key",
+                 "chunk_multi", "ndk_src", "ndk_dst", "phi", "ndk_sum"):
+        setattr(a, name, _lib.ptr(st[name]))
+    a.n_slices, a.K, a.KS, a.alpha, a.seed0, a.seed1 = n_slices, K, KS, float(alpha), s0, s1
+    a.sweep_lo, a.n_sweeps, a.avg_from, a.select = int(sweep_lo), int(n_sweeps), int(avg_from), int(select)
+    _lib.check(L.oni_foldin_launch(C.byref(a), G, KP, 1 if init else 0, _lib.stream()), "oni_foldin_launch")
 
 
 def _gibbs_flags(alpha_in_row: bool, word_init: bool, pos_aligned: bool) -> int:

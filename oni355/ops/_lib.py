@@ -86,8 +86,23 @@ _SIGS = {
     "oni_tile_score": [vp, vp, C.c_int, vp, vp, vp, vp, i64, vp, vp],
     "oni_wdelta_recount": [vp, vp, vp, i64, vp, C.c_int, C.c_int, vp],
 }
+class OniFoldin(C.Structure):
+    """Mirror of ``struct OniFoldin`` in csrc/kernels/foldin.hip (size checked at the first launch)."""
+
+    _fields_ = [
+        ("tok_word", vp), ("tok_z", vp), ("slice_off", vp), ("slice_len", vp),
+        ("chunk_doc", vp), ("chunk_pos0", vp), ("chunk_key", vp), ("chunk_multi", vp),
+        ("ndk_src", vp), ("ndk_dst", vp), ("phi", vp), ("ndk_sum", vp),
+        ("n_slices", i64), ("K", i32), ("KS", i32), ("alpha", f32), ("seed0", u32), ("seed1", u32),
+        ("sweep_lo", i32), ("n_sweeps", i32), ("avg_from", i32), ("select", i32),
+    ]
+
+
 # optional symbols (added by later kernel files); bound when present
-_OPTIONAL_SIGS: dict[str, list] = {}
+_OPTIONAL_SIGS: dict[str, list] = {
+    "oni_foldin_launch": [C.POINTER(OniFoldin), C.c_int, C.c_int, C.c_int, vp],
+    "oni_foldin_sizeof_args": [],
+}
 
 
 def _bind(h: C.CDLL, name: str, argtypes: list) -> None:

@@ -319,3 +319,100 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
                       dst_scores=parts[:, 1].cpu().numpy(), src_words=wparts[:, 0].cpu().numpy().view(np.uint32),
                       dst_words=wparts[:, 1].cpu().numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats,
                       lda=run)
+
+
+def model_word_ids(word_keys64: torch.Tensor, vocab: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """(int32 id of every word key in the saved model's sorted ``vocab``, number of keys absent
+    from it): an absent word gets id V, the table's out-of-vocabulary row."""
+    V = int(vocab.numel())
+    if V == 0:
+        return torch.zeros_like(word_keys64, dtype=torch.int32), int(word_keys64.numel())
+    pos = torch.searchsorted(vocab, word_keys64).clamp_(max=V - 1)
+    hit = vocab[pos] == word_keys64
+    wids = torch.where(hit, pos, torch.full_like(pos, V)).to(torch.int32).contiguous()
+    return wids, int(word_keys64.numel() - int(hit.sum()))
+
+
+@traced("oni:flow.score")
+def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
+               seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
+               feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
+               fuse: bool = True) -> FlowResult:
+    """Score a batch of flows against a saved model (``model``: models.saved.SavedModel) instead of
+    training on it: words from the model's cuts, ids through its vocabulary (unseen words → the
+    out-of-vocabulary row), the batch's own IP documents folded in against the frozen φ
+    (models.foldin.FoldIn), then the usual score plan / top-N against the model's table."""
+    from ..models.corpus import auto_chunk_len, build_corpus
+    from ..models.foldin import FoldIn
+    from ..models.gibbs import tiling_for
+    if comm is not None and comm.dist:
+        raise NotImplementedError("fold-in scoring is single-GPU")
+    if model.source != "flow":
+        raise ValueError(f"a {model.source} model cannot score flows")
+    if feedback and log:
+        log("analyst feedback is ignored when scoring against a saved model")
+    timer = StageTimer(device)
+    if device_cols is None:
+        cols = with_ipv6_keys(cols, None)
+    elif _needs_v6_keys(cols):
+        raise ValueError("score_flow(device_cols=...): IPv6 rows must be keyed with with_ipv6_keys() first")
+    with timer.stage("h2d"):
+        d = dict(device_cols) if device_cols is not None else to_device(cols, device)
+    with timer.stage("featurize"):
+        cuts = FlowCuts(model.cuts["time"], model.cuts["ibyt"], model.cuts["ipkt"])
+        sw, dw = wordify(d, cuts)
+    with timer.stage("vocab"):
+        n = d["sip"].numel()
+        dev = d["sip"].device
+        doc_keys = ops.widen_pair(d["sip"], d["dip"])
+        word_keys = ops.widen_pair(sw, dw)
+        vocab = torch.from_numpy(model.vocab).to(dev)
+        V = int(vocab.numel())
+        wids, n_oov = model_word_ids(word_keys, vocab)
+    with timer.stage("corpus"):
+        K = int(model.K)
+        G, KP = tiling_for(K, "dense")
+        if chunk_len <= 0:
+            chunk_len = auto_chunk_len(int(doc_keys.numel()), G)
+        udoc, inv = common.encode_docs(doc_keys)
+        D = int(udoc.numel())
+        pairs = None
+        if dev.type == "cuda":
+            from ..ops import corpus as oc
+            pairs = oc.pair_build(inv, wids, D, V + 1, None, n0=int(n))
+        corpus = build_corpus(inv, wids, D, V + 1, common.i64_to_u32bits(udoc), G, chunk_len, pairs=pairs)
+        table = model.table(G, KP, dev)
+    with timer.stage("foldin"):
+        fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse)
+        fold.run(sweeps, avg_last)
+    hist = torch.zeros(2048, dtype=torch.int32, device=dev)
+    with timer.stage("score_prep"):
+        theta = fold.theta()
+        if pairs is not None and not common.SCORE_TILES:
+            plan = common.plan_from_pairs(pairs, n, 2)
+        else:
+            # the torch reference plan over (doc row, word id) pairs (score_plan looks word KEYS up
+            # in the vocabulary, which unseen words are not in)
+            ids = inv.to(torch.int64) * (V + 1) + wids.to(torch.int64)
+            uniq, pinv = torch.unique(ids, return_inverse=True)
+            plan = common.ScorePlan((uniq // (V + 1)).to(torch.int32).contiguous(),
+                                    (uniq % (V + 1)).to(torch.int32).contiguous(),
+                                    [pinv[:n].to(torch.int32).contiguous(), pinv[n:].to(torch.int32).contiguous()])
+    with timer.stage("score"):
+        score, s1, s2 = common.plan_score(theta, table, plan, tol, hist=hist, want_parts=True)
+        rows, scs, rpos = common.top_n(score, tol, maxresults, None, row_offset, hist=hist, order=plan.order,
+                                       return_pos=True)
+    t = timer.summary()
+    t["records_scored"] = n
+    t["sweeps"] = int(sweeps)
+    li = rows - row_offset
+    ix = torch.stack([rpos, li]).to(dev)
+    parts = torch.stack([s1[ix[0]], s2[ix[0]]], 1).cpu()
+    wparts = torch.stack([sw[ix[1]], dw[ix[1]]], 1).cpu()
+    stats = corpus.stats()
+    stats.update({"n_flows": n, "loglik": None, "mode": "infer", "n_oov_tokens": n_oov,
+                  "foldin_launches": sum(fold.launches.values())})
+    stats.update({f"model_{k}": v for k, v in model.provenance.items() if isinstance(v, (int, float, str, bool))})
+    return FlowResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), src_scores=parts[:, 0].numpy(),
+                      dst_scores=parts[:, 1].numpy(), src_words=wparts[:, 0].numpy().view(np.uint32),
+                      dst_words=wparts[:, 1].numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats, lda=fold)
