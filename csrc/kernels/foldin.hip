@@ -190,41 +190,18 @@ int launch_foldin(const OniFoldin& a, bool init, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-template <int G>
-int dispatch_kp(const OniFoldin& a, int KP, bool init, hipStream_t s) {
-  switch (KP) {
-    case 12: return launch_foldin<G, 12>(a, init, s);
-    case 16: return launch_foldin<G, 16>(a, init, s);
-    case 20: return launch_foldin<G, 20>(a, init, s);
-    case 24: return launch_foldin<G, 24>(a, init, s);
-    case 28: return launch_foldin<G, 28>(a, init, s);
-    default: return (int)hipErrorInvalidValue;
-  }
-}
-
 }  // namespace
 
 ONI_API int oni_foldin_sizeof_args() { return (int)sizeof(OniFoldin); }
 
-// The tilings ops.choose_tiling returns for the dense sampler: G = 1 with KP = 4..32, G = 2 with
-// KP = 20..28, G = 4 with KP = 12..28, G = 8 and 16 with KP = 12 / 16. Anything else (and a launch
-// that would sweep a multi-chunk document more than once): hipErrorInvalidValue.
+// The tilings of the training samplers: the ONI_TILINGS table of gibbs_sampler.h. Anything else
+// (and a launch that would sweep a multi-chunk document more than once): hipErrorInvalidValue.
 ONI_API int oni_foldin_launch(const OniFoldin* a, int G, int KP, int init, hipStream_t s) {
   if (a == nullptr || a->K < 1 || a->K > G * KP || a->K > 255 || a->select < 0 || a->select > 2) return (int)hipErrorInvalidValue;
   if (!init && (a->n_sweeps < 1 || a->sweep_lo < 1 || (a->n_sweeps > 1 && a->select != 1))) return (int)hipErrorInvalidValue;
-  const bool in = init != 0;
-  switch (G) {
-    case 1:
-      switch (KP) {
-        case 4: return launch_foldin<1, 4>(*a, in, s);
-        case 8: return launch_foldin<1, 8>(*a, in, s);
-        case 32: return launch_foldin<1, 32>(*a, in, s);
-        default: return dispatch_kp<1>(*a, KP, in, s);
-      }
-    case 2: return KP >= 20 ? dispatch_kp<2>(*a, KP, in, s) : (int)hipErrorInvalidValue;
-    case 4: return dispatch_kp<4>(*a, KP, in, s);
-    case 8: return KP <= 16 ? dispatch_kp<8>(*a, KP, in, s) : (int)hipErrorInvalidValue;
-    case 16: return KP <= 16 ? dispatch_kp<16>(*a, KP, in, s) : (int)hipErrorInvalidValue;
-    default: return (int)hipErrorInvalidValue;
-  }
+#define ONI_FOLDIN_CASE(g_, kp_) \
+  if (G == g_ && KP == kp_) return launch_foldin<g_, kp_>(*a, init != 0, s);
+  ONI_TILINGS(ONI_FOLDIN_CASE)
+#undef ONI_FOLDIN_CASE
+  return (int)hipErrorInvalidValue;
 }

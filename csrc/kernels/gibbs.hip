@@ -474,12 +474,12 @@ ONI_API int oni_recount_stream(const int32_t* wsorted, const uint8_t* z_w, int64
   return (int)hipErrorInvalidValue;
 }
 
-// Supported (G, KP) configurations. K ≤ 32: G = 1 (KP = K rounded up to 4).
+// Supported (G, KP) configurations: the ONI_TILINGS table of gibbs_sampler.h.
 static int gibbs_dispatch(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which) {
   switch (G) {
-    case 1: return oni_gibbs_dispatch_g1(a, KP, init, mode, qpf, s, which);
-    case 2: return oni_gibbs_dispatch_g2(a, KP, init, mode, qpf, s, which);
-    case 4: return oni_gibbs_dispatch_g4(a, KP, init, mode, qpf, s, which);
+    case 1: return oni_gibbs_dispatch_g1(a, G, KP, init, mode, qpf, s, which);
+    case 2: return oni_gibbs_dispatch_g2(a, G, KP, init, mode, qpf, s, which);
+    case 4: return oni_gibbs_dispatch_g4(a, G, KP, init, mode, qpf, s, which);
     case 8:
     case 16: return oni_gibbs_dispatch_g8(a, G, KP, init, mode, qpf, s, which);
     default: break;

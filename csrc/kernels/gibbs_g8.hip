@@ -2,10 +2,10 @@
 #include "gibbs_sampler.h"
 
 int oni_gibbs_dispatch_g8(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which) {
-#define ONI_CASE(g_, kp_) \
+#define ONI_GIBBS_CASE(g_, kp_) \
   if (G == g_ && KP == kp_) return launch_gibbs<g_, kp_>(a, init, mode, qpf, s, which);
-  ONI_CASE(8, 8) ONI_CASE(8, 12) ONI_CASE(8, 16)
-  ONI_CASE(16, 8) ONI_CASE(16, 16)
-#undef ONI_CASE
+  ONI_TILINGS_G8(ONI_GIBBS_CASE)
+  ONI_TILINGS_G16(ONI_GIBBS_CASE)
+#undef ONI_GIBBS_CASE
   return (int)hipErrorInvalidValue;
 }

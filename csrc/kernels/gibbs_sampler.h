@@ -1214,11 +1214,22 @@ int select_gibbs(const OniGibbs& a, bool init, int mode, int qpf, F&& f) {
 
 }  // namespace
 
+// The supported tilings (G lanes per unit, KP topics per lane): THE list. Training (the
+// dispatchers below) and fold-in (oni_foldin_launch) instantiate exactly these pairs, and every
+// pair ops.choose_tiling returns must be among them (tests/test_tiling_table_cpu.py). One list per
+// lane count, so each gibbs_g*.hip instantiates its own share and they compile in parallel.
+#define ONI_TILINGS_G1(X) X(1, 4) X(1, 8) X(1, 12) X(1, 16) X(1, 20) X(1, 24) X(1, 28) X(1, 32)
+#define ONI_TILINGS_G2(X) X(2, 20) X(2, 24) X(2, 28)
+#define ONI_TILINGS_G4(X) X(4, 8) X(4, 12) X(4, 16) X(4, 20) X(4, 24) X(4, 28)
+#define ONI_TILINGS_G8(X) X(8, 8) X(8, 12) X(8, 16)
+#define ONI_TILINGS_G16(X) X(16, 8) X(16, 16)
+#define ONI_TILINGS(X) ONI_TILINGS_G1(X) ONI_TILINGS_G2(X) ONI_TILINGS_G4(X) ONI_TILINGS_G8(X) ONI_TILINGS_G16(X)
+
 // Per-unit-width dispatchers (gibbs_g1.hip, gibbs_g2.hip, gibbs_g4.hip, gibbs_g8.hip): launch
-// launch_gibbs<G, KP> for a supported KP; hipErrorInvalidValue otherwise. which != nullptr: the
-// query (no launch, see launch_gibbs).
-int oni_gibbs_dispatch_g1(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
-int oni_gibbs_dispatch_g2(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
-int oni_gibbs_dispatch_g4(const OniGibbs& a, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
-int oni_gibbs_dispatch_g8(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s,
-                          int* which);
+// launch_gibbs<G, KP> for a pair of their share of the table (each expands its ONI_TILINGS_G* list
+// with a local case macro); hipErrorInvalidValue otherwise.
+// which != nullptr: the query (no launch, see launch_gibbs).
+int oni_gibbs_dispatch_g1(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
+int oni_gibbs_dispatch_g2(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
+int oni_gibbs_dispatch_g4(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);
+int oni_gibbs_dispatch_g8(const OniGibbs& a, int G, int KP, bool init, int mode, int qpf, hipStream_t s, int* which);

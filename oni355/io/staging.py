@@ -30,14 +30,14 @@ import torch
 from ..ops import _lib
 
 vp, i64 = C.c_void_p, C.c_int64
-_lib.register_optional("oni_stager_create", [i64, C.c_int, C.c_int, C.POINTER(C.c_void_p)])
-_lib.register_optional("oni_stager_upload", [vp, vp, vp, i64, vp])
-_lib.register_optional("oni_stager_sync", [vp])
-_lib.register_optional("oni_stager_stats", [vp, vp])
-_lib.register_optional("oni_stager_destroy", [vp])
-_lib.register_optional("oni_h2d_registered", [vp, vp, i64, vp])
-_lib.register_optional("oni_h2d_pull", [vp, vp, i64, C.c_int, vp])
-_lib.register_optional("oni_d2h_push", [vp, vp, i64, vp])
+_lib.register("oni_stager_create", [i64, C.c_int, C.c_int, C.POINTER(C.c_void_p)])
+_lib.register("oni_stager_upload", [vp, vp, vp, i64, vp])
+_lib.register("oni_stager_sync", [vp])
+_lib.register("oni_stager_stats", [vp, vp])
+_lib.register("oni_stager_destroy", [vp])
+_lib.register("oni_h2d_registered", [vp, vp, i64, vp])
+_lib.register("oni_h2d_pull", [vp, vp, i64, C.c_int, vp])
+_lib.register("oni_d2h_push", [vp, vp, i64, vp])
 
 # Prefetcher uploads: "dma" (hipMemcpyAsync) or "pull" (CUs read the pinned host buffers and the
 # DMA engine stays free). Measured (bench/overlap_probe.py, profiles/r2_copy_overlap_probe.txt):

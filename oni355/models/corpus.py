@@ -77,6 +77,13 @@ class Corpus:
     def sell_slots(self) -> int:
         return int(self.tok_word.numel())
 
+    def sell_state(self, tok_z: torch.Tensor) -> dict:
+        """The SELL-layout entries of a sampler's state dict (ops.gibbs_pass / ops.foldin_pass);
+        ``tok_z``: the sampler's own topic array in this layout."""
+        return dict(tok_word=self.tok_word, tok_z=tok_z, slice_off=self.slice_off, slice_len=self.slice_len,
+                    chunk_doc=self.chunk_doc, chunk_pos0=self.chunk_pos0, chunk_key=self.chunk_key,
+                    chunk_multi=self.chunk_multi)
+
     def doc_lengths(self) -> torch.Tensor:
         return self.doc_tok_ptr[1:] - self.doc_tok_ptr[:-1]
 

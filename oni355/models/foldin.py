@@ -49,10 +49,7 @@ class FoldIn:
         self.launches = {"init": 0, "sweep": 0, "multi_sweep": 0}
 
     def _state(self, src: torch.Tensor, dst: torch.Tensor) -> dict:
-        c = self.c
-        return dict(tok_word=c.tok_word, tok_z=self.tok_z, slice_off=c.slice_off, slice_len=c.slice_len,
-                    chunk_doc=c.chunk_doc, chunk_pos0=c.chunk_pos0, chunk_key=c.chunk_key,
-                    chunk_multi=c.chunk_multi, ndk_src=src, ndk_dst=dst, ndk_sum=self.ndk_sum, phi=self.table)
+        return dict(self.c.sell_state(self.tok_z), ndk_src=src, ndk_dst=dst, ndk_sum=self.ndk_sum, phi=self.table)
 
     def _pass(self, st: dict, init: bool, sweep_lo: int, n_sweeps: int, avg_from: int, select: int) -> None:
         ops.foldin_pass(st, self.G, self.KP, self.K, self.alpha, self.seed, init, sweep_lo, n_sweeps, avg_from,

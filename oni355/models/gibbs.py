@@ -485,10 +485,10 @@ class GibbsLDA:
     # ---------------------------------------------------------------------------------------------
     def _state(self, init: bool) -> dict:
         c = self.c
-        # the sampler reads chunk_pos0 only as the Philox position: split pieces use global ones
-        st = dict(tok_word=c.tok_word, tok_z=self.tok_z, slice_off=c.slice_off, slice_len=c.slice_len,
-                  chunk_doc=c.chunk_doc, chunk_pos0=c.chunk_rng0 if c.chunk_rng0 is not None else c.chunk_pos0,
-                  chunk_key=c.chunk_key, chunk_multi=c.chunk_multi, q=self.q, qfix=self.qfix)
+        st = dict(c.sell_state(self.tok_z), q=self.q, qfix=self.qfix)
+        if c.chunk_rng0 is not None:
+            # the sampler reads chunk_pos0 only as the Philox position: split pieces use global ones
+            st["chunk_pos0"] = c.chunk_rng0
         VK = self.V * self.KS
         if init:
             st.update(ndk_src=self.ndk[0], ndk_dst=self.ndk[0], dnwk=self.nwk, dnk=self.nk[0])

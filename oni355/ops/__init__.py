@@ -47,6 +47,30 @@ def _need(t: torch.Tensor, dtype: torch.dtype, name: str, n: int | None = None) 
         raise ValueError(f"{name}: expected {n} elements, got {t.numel()}")
 
 
+# host plumbing shared by the samplers' passes (gibbs_pass, foldin_pass)
+_SAMPLER_LAYOUT = ("tok_word", "tok_z", "slice_off", "slice_len", "chunk_doc", "chunk_pos0", "chunk_key",
+                   "chunk_multi", "ndk_src", "ndk_dst")
+
+
+def _np_state(st: dict, u32_keys: tuple) -> dict:
+    """The NumPy view of a (CPU) torch state dict for the oracle; ``u32_keys`` are viewed as uint32."""
+    return {k: (v.numpy().view(np.uint32) if k in u32_keys else v.numpy())
+            for k, v in st.items() if isinstance(v, torch.Tensor)}
+
+
+def _fill_ptrs(a: C.Structure, st: dict, names: tuple) -> None:
+    for name in names:
+        setattr(a, name, _lib.ptr(st[name]))
+
+
+def _check_layout(st: dict, G: int, KS: int, rows: tuple) -> None:
+    """The tables ``rows`` (the word table first) are KS wide; the chunk table matches the slices."""
+    if any(st[k].shape[-1] != KS for k in rows):
+        raise ValueError(f"{rows[0]} / ndk row width must equal G*KP")
+    if st["chunk_doc"].numel() != st["slice_len"].numel() * (64 // G):
+        raise ValueError("chunk table must hold S chunks per slice")
+
+
 # ------------------------------------------------------------------------------------------------
 # tiling choice for the sampler: (G lanes per unit, KP topics per lane)
 # ------------------------------------------------------------------------------------------------
@@ -404,8 +428,7 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
     if not _is_dev(st["tok_word"]):
         chg = st.get("chg_count")
         z_before = st["tok_z"].clone() if (chg is not None or mode == 4) else None
-        npst = {k: (v.numpy().view(np.uint32) if k in ("tok_word", "chunk_key", "walias", "dalias") else v.numpy())
-                for k, v in st.items() if isinstance(v, torch.Tensor)}
+        npst = _np_state(st, ("tok_word", "chunk_key", "walias", "dalias"))
         npst["dnk"] = npst["dnk"][:KS]  # replica 0 (the sum over replicas is what counts)
         if mode != 1:
             npst["dnwk"] = np.zeros_like(npst["dnwk"])  # discarded: recount rebuilds n_wk
@@ -434,15 +457,9 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
         if chg is not None:
             chg += int((st["tok_z"] != z_before).sum())
         return
-    n_slices = st["slice_len"].numel()
-    if st["q"].shape[-1] != KS or st["ndk_src"].shape[-1] != KS:
-        raise ValueError("q / ndk row width must equal G*KP")
-    if st["chunk_doc"].numel() != n_slices * (64 // G):
-        raise ValueError("chunk table must hold S chunks per slice")
+    _check_layout(st, G, KS, ("q", "ndk_src"))
     a = _lib.OniGibbs()
-    for name in ("tok_word", "tok_z", "slice_off", "slice_len", "chunk_doc", "chunk_pos0", "chunk_key",
-                 "chunk_multi", "ndk_src", "ndk_dst", "q", "dnwk", "dnk"):
-        setattr(a, name, _lib.ptr(st[name]))
+    _fill_ptrs(a, st, _SAMPLER_LAYOUT + ("q", "dnwk", "dnk"))
     if not init:
         a.qfix = _lib.ptr(st["qfix"])
     a.sweep_ctr = _lib.ptr(sweep_ctr)
@@ -466,7 +483,7 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
         if st["tok_zlag"].numel() != st["tok_z"].numel() or st["tok_zlag"].dtype != torch.uint8:
             raise ValueError("tok_zlag must be a uint8 SELL array like tok_z")
         a.tok_zlag = _lib.ptr(st["tok_zlag"])
-    a.n_slices, a.K, a.KS, a.alpha, a.seed0, a.seed1 = n_slices, K, KS, float(alpha), s0, s1
+    a.n_slices, a.K, a.KS, a.alpha, a.seed0, a.seed1 = st["slice_len"].numel(), K, KS, float(alpha), s0, s1
     a.nk_rep = nk_rep
     # the caller vouches that n + α is exact in f32 for every doc-topic count of this corpus
     # ONI_SAMPLER_AB (kernel A/B, bench/sampler_ab.py): bit 0 = word-sorted slots loaded on change
@@ -489,8 +506,7 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
         m.inv_alpha = float(np.float32(1.0 / alpha))
         m.doc_moves = int(mh_doc_moves)
         if not init:
-            for name in ("dalias", "chunk_dslot"):
-                setattr(m, name, _lib.ptr(st[name]))
+            _fill_ptrs(m, st, ("dalias", "chunk_dslot"))
             if st.get("wcdf") is not None:
                 m.wcdf, m.wp = _lib.ptr(st["wcdf"]), (8 if K <= 128 else 16)
             else:
@@ -527,8 +543,7 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
     elif n_sweeps > 1 and select != 1:
         raise ValueError("only single-chunk documents run several sweeps in one launch (select=1)")
     KS = G * KP
-    if st["phi"].shape[-1] != KS or st["ndk_src"].shape[-1] != KS or st["ndk_dst"].shape[-1] != KS:
-        raise ValueError("phi / ndk row width must equal G*KP")
+    _check_layout(st, G, KS, ("phi", "ndk_src", "ndk_dst"))
     if st["ndk_sum"].shape != st["ndk_dst"].shape or st["ndk_sum"].dtype != torch.int32:
         raise ValueError("ndk_sum must be an int32 table of the doc rows' shape")
     in_place = st["ndk_src"].data_ptr() == st["ndk_dst"].data_ptr()
@@ -536,8 +551,7 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
         raise ValueError("multi-chunk documents add their deltas into a pre-copied row of another buffer")
     s0, s1 = spec.split_seed(seed)
     if not _is_dev(st["tok_word"]):
-        npst = {k: (v.numpy().view(np.uint32) if k in ("tok_word", "chunk_key") else v.numpy())
-                for k, v in st.items() if isinstance(v, torch.Tensor)}
+        npst = _np_state(st, ("tok_word", "chunk_key"))
         cl = chunk_len.numpy()
         if init:
             foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, True, 0, cl, select)
@@ -549,21 +563,11 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
             if sweep >= avg_from and select != 2:
                 npst["ndk_sum"][docs] += npst["ndk_dst"][docs]
         return
-    n_slices = st["slice_len"].numel()
-    if st["chunk_doc"].numel() != n_slices * (64 // G):
-        raise ValueError("chunk table must hold S chunks per slice")
-    L = _lib.lib()
-    if not hasattr(L, "oni_foldin_launch"):
-        raise RuntimeError("liboni_hip.so has no fold-in kernel (oni_foldin_launch): rebuild with `python tools/build.py`")
-    if L.oni_foldin_sizeof_args() != C.sizeof(_lib.OniFoldin):
-        raise RuntimeError("OniFoldin ABI mismatch between Python and liboni_hip.so; rebuild")
     a = _lib.OniFoldin()
-    for name in ("tok_word", "tok_z", "slice_off", "slice_len", "chunk_doc", "chunk_pos0", "chunk_key",
-                 "chunk_multi", "ndk_src", "ndk_dst", "phi", "ndk_sum"):
-        setattr(a, name, _lib.ptr(st[name]))
-    a.n_slices, a.K, a.KS, a.alpha, a.seed0, a.seed1 = n_slices, K, KS, float(alpha), s0, s1
+    _fill_ptrs(a, st, _SAMPLER_LAYOUT + ("phi", "ndk_sum"))
+    a.n_slices, a.K, a.KS, a.alpha, a.seed0, a.seed1 = st["slice_len"].numel(), K, KS, float(alpha), s0, s1
     a.sweep_lo, a.n_sweeps, a.avg_from, a.select = int(sweep_lo), int(n_sweeps), int(avg_from), int(select)
-    _lib.check(L.oni_foldin_launch(C.byref(a), G, KP, 1 if init else 0, _lib.stream()), "oni_foldin_launch")
+    _lib.check(_lib.lib().oni_foldin_launch(C.byref(a), G, KP, 1 if init else 0, _lib.stream()), "oni_foldin_launch")
 
 
 def _gibbs_flags(alpha_in_row: bool, word_init: bool, pos_aligned: bool) -> int:

@@ -47,7 +47,21 @@ class OniMH(C.Structure):
     ]
 
 
-_SIGS = {
+class OniFoldin(C.Structure):
+    """Mirror of ``struct OniFoldin`` in csrc/kernels/foldin.hip (size checked at load)."""
+
+    _fields_ = [
+        ("tok_word", vp), ("tok_z", vp), ("slice_off", vp), ("slice_len", vp),
+        ("chunk_doc", vp), ("chunk_pos0", vp), ("chunk_key", vp), ("chunk_multi", vp),
+        ("ndk_src", vp), ("ndk_dst", vp), ("phi", vp), ("ndk_sum", vp),
+        ("n_slices", i64), ("K", i32), ("KS", i32), ("alpha", f32), ("seed0", u32), ("seed1", u32),
+        ("sweep_lo", i32), ("n_sweeps", i32), ("avg_from", i32), ("select", i32),
+    ]
+
+
+# every launcher of the library: name -> argtypes (all return int). Modules with launchers of their
+# own add theirs with register() at import.
+_REGISTRY: dict[str, list] = {
     "oni_radix_hist": [vp, i64, C.c_int, C.c_int, vp, C.c_int, u32, vp, vp],
     "oni_f32_keys": [vp, i64, vp, vp],
     "oni_i64_keys": [vp, i64, vp, vp],
@@ -85,39 +99,33 @@ _SIGS = {
     "oni_event_min": [vp, vp, vp, i64, f32, vp, vp, vp, vp, vp],
     "oni_tile_score": [vp, vp, C.c_int, vp, vp, vp, vp, i64, vp, vp],
     "oni_wdelta_recount": [vp, vp, vp, i64, vp, C.c_int, C.c_int, vp],
-}
-class OniFoldin(C.Structure):
-    """Mirror of ``struct OniFoldin`` in csrc/kernels/foldin.hip (size checked at the first launch)."""
-
-    _fields_ = [
-        ("tok_word", vp), ("tok_z", vp), ("slice_off", vp), ("slice_len", vp),
-        ("chunk_doc", vp), ("chunk_pos0", vp), ("chunk_key", vp), ("chunk_multi", vp),
-        ("ndk_src", vp), ("ndk_dst", vp), ("phi", vp), ("ndk_sum", vp),
-        ("n_slices", i64), ("K", i32), ("KS", i32), ("alpha", f32), ("seed0", u32), ("seed1", u32),
-        ("sweep_lo", i32), ("n_sweeps", i32), ("avg_from", i32), ("select", i32),
-    ]
-
-
-# optional symbols (added by later kernel files); bound when present
-_OPTIONAL_SIGS: dict[str, list] = {
     "oni_foldin_launch": [C.POINTER(OniFoldin), C.c_int, C.c_int, C.c_int, vp],
     "oni_foldin_sizeof_args": [],
 }
+# argument structs whose size the library reports: checked against the mirrors above at load
+_ARG_STRUCTS = {"oni_gibbs_sizeof_args": OniGibbs, "oni_mh_sizeof_args": OniMH, "oni_foldin_sizeof_args": OniFoldin}
 
 
 def _bind(h: C.CDLL, name: str, argtypes: list) -> None:
-    fn = getattr(h, name)
+    # the build links every csrc/kernels/*.hip into the one library, so a symbol of this tree is
+    # missing only from a stale or broken build: no "bind if present"
+    try:
+        fn = getattr(h, name)
+    except AttributeError:
+        raise RuntimeError(f"{HIP_LIB_PATH} has no symbol {name}: stale or broken build, "
+                           "rebuild with `python tools/build.py`") from None
     fn.argtypes = argtypes
     fn.restype = C.c_int
 
 
-def register_optional(name: str, argtypes: list) -> None:
+def register(name: str, argtypes: list) -> None:
     """Declare a launcher's C signature. Binds at once if the library is already loaded: an
     unbound ctypes function would pass 64-bit device pointers as 32-bit C ints (silently
-    truncated), so a module imported after the first kernel launch must not stay unbound."""
+    truncated), so a module imported after the first kernel launch must not stay unbound.
+    A symbol the library lacks raises, here or when the library loads."""
     with _lock:
-        _OPTIONAL_SIGS[name] = argtypes
-        if _lib is not None and hasattr(_lib, name):
+        _REGISTRY[name] = argtypes
+        if _lib is not None:
             _bind(_lib, name, argtypes)
 
 
@@ -134,15 +142,11 @@ def lib() -> C.CDLL:
                 f"oni355 HIP kernels not built: {HIP_LIB_PATH} missing. Run `python tools/build.py`."
             )
         h = C.CDLL(HIP_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, args in _SIGS.items():
+        for name, args in _REGISTRY.items():
             _bind(h, name, args)
-        for name, args in _OPTIONAL_SIGS.items():
-            if hasattr(h, name):
-                _bind(h, name, args)
-        if h.oni_mh_sizeof_args() != C.sizeof(OniMH):
-            raise RuntimeError("OniMH layout mismatch between liboni_hip.so and oni355/ops/_lib.py")
-        if h.oni_gibbs_sizeof_args() != C.sizeof(OniGibbs):
-            raise RuntimeError("OniGibbs ABI mismatch between Python and liboni_hip.so; rebuild")
+        for name, struct in _ARG_STRUCTS.items():
+            if getattr(h, name)() != C.sizeof(struct):
+                raise RuntimeError(f"{struct.__name__} ABI mismatch between Python and liboni_hip.so; rebuild")
         from ..utils import provenance
         h.oni_hip_src_hash.restype = C.c_char_p
         h.oni_hip_src_hash.argtypes = []

@@ -17,19 +17,19 @@ from . import _lib
 
 vp, i64, ci = C.c_void_p, C.c_int64, C.c_int
 _SZ = C.POINTER(C.c_size_t)
-_lib.register_optional("oni_dict_encode", [vp, i64, ci, vp, vp, vp, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_hashdict_build", [vp, i64, i64, vp, vp, vp, vp, vp])
-_lib.register_optional("oni_hashdict_finish", [vp, i64, ci, i64, vp, vp, vp, i64, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_route_pack", [vp, vp, vp, vp, vp, i64, ci, vp, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_route_pack_ids", [vp, vp, vp, vp, vp, i64, ci, vp, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_route_unpack", [vp, i64, ci, vp, vp, ci, vp, vp, vp, vp, vp])
-_lib.register_optional("oni_partition", [vp, vp, vp, i64, ci, vp, vp, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_place_stats", [vp, vp, i64, vp, i64, ci, vp, vp])
-_lib.register_optional("oni_place_owner", [vp, i64, vp, i64, vp, ci, vp, vp, vp])
-_lib.register_optional("oni_pair_build", [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, _SZ, vp])
-_lib.register_optional("oni_doc_layout", [vp, vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_chunk_layout", [vp, vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, _SZ, vp])
-_lib.register_optional("oni_word_index", [vp, i64, i64, i64, ci, vp, vp, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_dict_encode", [vp, i64, ci, vp, vp, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_hashdict_build", [vp, i64, i64, vp, vp, vp, vp, vp])
+_lib.register("oni_hashdict_finish", [vp, i64, ci, i64, vp, vp, vp, i64, vp, vp, vp, _SZ, vp])
+_lib.register("oni_route_pack", [vp, vp, vp, vp, vp, i64, ci, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_route_pack_ids", [vp, vp, vp, vp, vp, i64, ci, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_route_unpack", [vp, i64, ci, vp, vp, ci, vp, vp, vp, vp, vp])
+_lib.register("oni_partition", [vp, vp, vp, i64, ci, vp, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_place_stats", [vp, vp, i64, vp, i64, ci, vp, vp])
+_lib.register("oni_place_owner", [vp, i64, vp, i64, vp, ci, vp, vp, vp])
+_lib.register("oni_pair_build", [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, _SZ, vp])
+_lib.register("oni_doc_layout", [vp, vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_chunk_layout", [vp, vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, _SZ, vp])
+_lib.register("oni_word_index", [vp, i64, i64, i64, ci, vp, vp, vp, vp, vp, vp, _SZ, vp])
 
 
 def _call(name: str, *args) -> None:

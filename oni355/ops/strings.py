@@ -23,14 +23,14 @@ class OniPack(C.Structure):
     ]
 
 
-_lib.register_optional("oni_domain_features", [vp, vp, i64, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp,
+_lib.register("oni_domain_features", [vp, vp, i64, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp,
                                                vp, C.c_uint64, vp, C.c_uint64, C.c_int,
                                                vp, vp, vp, vp, vp, vp])
-_lib.register_optional("oni_string_features", [vp, vp, i64, vp, vp, vp, vp, vp, vp])
-_lib.register_optional("oni_set_probe", [vp, i64, vp, C.c_uint64, vp, vp])
-_lib.register_optional("oni_pack_words", [C.POINTER(OniPack), vp])
-_lib.register_optional("oni_category_codes", [vp, vp, i64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp])
-_lib.register_optional("oni_pack_sizeof", [])
+_lib.register("oni_string_features", [vp, vp, i64, vp, vp, vp, vp, vp, vp])
+_lib.register("oni_set_probe", [vp, i64, vp, C.c_uint64, vp, vp])
+_lib.register("oni_pack_words", [C.POINTER(OniPack), vp])
+_lib.register("oni_category_codes", [vp, vp, i64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp])
+_lib.register("oni_pack_sizeof", [])
 
 _tables: dict = {}
 

@@ -21,7 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import spec
-from .spec import F32, U32, fma_f32, token_rand, u01
+from .spec import F32, U32, token_rand
 
 SELECT_ALL, SELECT_SINGLE, SELECT_MULTI = 0, 1, 2
 
@@ -32,8 +32,8 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, see
 
     Per chunk: ``n`` starts at zero (init) or at ``ndk_src[doc]``; tokens are taken in chunk order.
     Per token: on a sweep ``n[zo] -= 1``; a_j = f32(n_j) + f32(α); lane g chains its KP topics,
-    P_j = fma(a_j, φ_wj, P_{j−1}); lanes are combined by the Hillis-Steele scan of the G > 1 branch
-    of :func:`spec.gibbs_pass`; thr = u01(r)·total; zn = min(#{cum ≤ thr}, K − 1); ``n[zn] += 1``,
+    P_j = fma(a_j, φ_wj, P_{j−1}); lanes are combined, and the topic drawn, by the training oracle's
+    own :func:`spec.unit_draw`: thr = u01(r)·total; zn = min(#{cum ≤ thr}, K − 1); ``n[zn] += 1``,
     ``tok_z = zn``. The init pass is the same code without the decrement: a chunk's tokens are drawn
     one after another from (n_so_far + α)·φ_w. Epilogue as in gibbs_pass: a single-chunk document
     writes its row to ``ndk_dst``, a multi-chunk document adds its Δ.
@@ -76,29 +76,7 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, see
             zo = st["tok_z"][idx].astype(np.int64)
             n[act, zo] -= 1
         av = (n[act].astype(F32) + alpha32).reshape(-1, G, KP)
-        qg = phi[w].reshape(-1, G, KP)
-        loc = np.empty_like(av)
-        run = np.zeros(av.shape[:2], dtype=F32)
-        for j in range(KP):
-            run = fma_f32(av[:, :, j], qg[:, :, j], run)
-            loc[:, :, j] = run
-        if G == 1:
-            cum = loc.reshape(-1, KS)
-            total = cum[:, -1]
-        else:
-            incl = loc[:, :, -1].copy()
-            d = 1
-            while d < G:
-                prev = incl.copy()
-                incl[:, d:] = prev[:, d:] + prev[:, :-d]
-                d <<= 1
-            excl = np.zeros_like(incl)
-            excl[:, 1:] = incl[:, :-1]
-            cum = (excl[:, :, None] + loc).reshape(-1, KS)
-            total = incl[:, -1]
-        thr = u01(rr) * total
-        cnt = (cum <= thr[:, None]).sum(axis=1)
-        zn = np.minimum(cnt, K - 1).astype(np.int64)
+        zn = spec.unit_draw(av, phi[w].reshape(-1, G, KP), rr, K)
         n[act, zn] += 1
         st["tok_z"][idx] = zn.astype(np.uint8)
     d = n - n_start

@@ -290,6 +290,39 @@ def excluded_q(qz: np.ndarray, zo: np.ndarray, qfix: np.ndarray) -> np.ndarray:
     return fma_f32(qz.astype(F32), qfix[0][zo], -qfix[1][zo])
 
 
+def unit_draw(av: np.ndarray, qg: np.ndarray, rr: np.ndarray, K: int) -> np.ndarray:
+    """THE topic draw of a sampler unit, shared by :func:`gibbs_pass` and
+    :func:`oni355.ref.foldin_spec.foldin_pass`. ``av`` / ``qg``: f32 [A, G, KP], the doc-side and
+    word-side factors of A units of G lanes with KP topics each; ``rr``: u32 [A], one Philox word
+    per unit. Lane g chains its topics, P_j = fma(av_j, qg_j, P_{j−1}); the lanes' totals are combined
+    by a Hillis-Steele inclusive scan (the kernels' shuffle / DPP scan, same additions in the same
+    order) and each lane's prefix is offset by the exclusive value; thr = u01(r)·total;
+    zn = min(#{cum ≤ thr}, K − 1), int64 [A]."""
+    _, G, KP = av.shape
+    loc = np.empty_like(av)
+    run = np.zeros(av.shape[:2], dtype=F32)
+    for j in range(KP):
+        run = fma_f32(av[:, :, j], qg[:, :, j], run)
+        loc[:, :, j] = run
+    if G == 1:
+        cum = loc.reshape(-1, KP)
+        total = cum[:, -1]
+    else:
+        incl = loc[:, :, -1].copy()
+        d = 1
+        while d < G:
+            prev = incl.copy()
+            incl[:, d:] = prev[:, d:] + prev[:, :-d]
+            d <<= 1
+        excl = np.zeros_like(incl)
+        excl[:, 1:] = incl[:, :-1]
+        cum = (excl[:, :, None] + loc).reshape(-1, G * KP)
+        total = incl[:, -1]
+    thr = u01(rr) * total
+    cnt = (cum <= thr[:, None]).sum(axis=1)
+    return np.minimum(cnt, K - 1).astype(np.int64)
+
+
 def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, seed1: int, init: bool,
                sweep: int, chunk_len: np.ndarray, word_init: bool = False):
     """One init (init=True) or sweep pass over numpy state arrays, in place.
@@ -367,30 +400,7 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, seed
         else:
             f = (qe / qz).astype(F32)
             av[ar, zl] = (av[ar, zl] * f).astype(F32)
-        avg = av.reshape(-1, G, KP)
-        qg = qv.reshape(-1, G, KP)
-        loc = np.empty_like(avg)
-        run = np.zeros(avg.shape[:2], dtype=F32)
-        for j in range(KP):
-            run = fma_f32(avg[:, :, j], qg[:, :, j], run)
-            loc[:, :, j] = run
-        if G == 1:
-            cum = loc.reshape(-1, KS)
-            total = cum[:, -1]
-        else:
-            incl = loc[:, :, -1].copy()
-            d = 1
-            while d < G:
-                prev = incl.copy()
-                incl[:, d:] = prev[:, d:] + prev[:, :-d]
-                d <<= 1
-            excl = np.zeros_like(incl)
-            excl[:, 1:] = incl[:, :-1]
-            cum = (excl[:, :, None] + loc).reshape(-1, KS)
-            total = incl[:, -1]
-        thr = u01(rr) * total
-        cnt = (cum <= thr[:, None]).sum(axis=1)
-        zn = np.minimum(cnt, K - 1).astype(np.int64)
+        zn = unit_draw(av.reshape(-1, G, KP), qv.reshape(-1, G, KP), rr, K)
         n[act, zn] += 1
         ch = zn != zo
         if lag:

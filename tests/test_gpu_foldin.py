@@ -1,5 +1,6 @@
 """k_foldin (csrc/kernels/foldin.hip) against its oracle (oni355/ref/foldin_spec.py), bit for bit
-on tok_z, ndk and ndk_sum, for the dense tilings (1,12), (1,20), (2,28), (4,28), (8,16).
+on tok_z, ndk and ndk_sum, for the dense tilings (1,12), (1,20), (2,28), (4,28), (8,16), and for
+(4,8) and (16,8) of the training samplers' table, which ops.choose_tiling never returns.
 
 The corpus is hand-built (≤ 4k tokens, 64 words + the out-of-vocabulary row) with the shapes where
 the kernel can go wrong: a 1-token document, chunks of exactly the chunk length, a chunk length
@@ -75,9 +76,9 @@ def _oracle(c, table, G, KP, K, sweeps, avg_last):
     return st["tok_z"], ndk, ndk_sum
 
 
-def _check(gpu, K, sweeps, avg_last, fuse=True, multi=True):
-    G, KP = ops.choose_tiling(K)
-    assert (G, KP) == TILINGS[K]
+def _check(gpu, K, sweeps, avg_last, fuse=True, multi=True, tiling=None):
+    G, KP = tiling or ops.choose_tiling(K)
+    assert tiling or (G, KP) == TILINGS[K]
     c = _corpus(G, multi)
     table = _table(K, G * KP)
     want_z, want_n, want_sum = _oracle(c, table, G, KP, K, sweeps, avg_last)
@@ -95,6 +96,18 @@ def _check(gpu, K, sweeps, avg_last, fuse=True, multi=True):
 def test_device_replays_the_oracle(gpu, K, sweeps, avg_last):
     f = _check(gpu, K, sweeps, avg_last)
     assert f.launches == {"init": 1, "sweep": 1, "multi_sweep": sweeps}
+
+
+# tilings of the training samplers' table that choose_tiling never returns (the widest units among
+# them): the corpus is built for that G explicitly, K < KS
+@pytest.mark.parametrize("G,KP,K", [(4, 8, 30), (16, 8, 120)])
+def test_table_tilings_choose_tiling_never_picks(gpu, G, KP, K):
+    assert all(ops.choose_tiling(k) != (G, KP) for k in range(1, 256))
+    c = _corpus(G)
+    start = c.chunk_pos0[c.chunk_doc >= 0]
+    assert bool(c.chunk_multi.any()) and bool((start % 4 != 0).any())
+    f = _check(gpu, K, 2, 2, tiling=(G, KP))
+    assert f.launches == {"init": 1, "sweep": 1, "multi_sweep": 2}
 
 
 @pytest.mark.parametrize("K", [20, 100])

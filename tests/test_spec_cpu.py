@@ -354,3 +354,23 @@ def test_auto_mode_stops_polling_far_above_threshold():
     assert a._poll_off and not a._delta_on
     assert max(sw for sw, _ in a.change_log) < gm.POLL_GIVE_UP_SWEEP + 4
     assert torch.equal(a.tok_z, b.tok_z) and torch.equal(a.nwk, b.nwk)
+
+
+# --- the one topic draw of the oracle (spec.unit_draw: gibbs_pass and foldin_spec.foldin_pass) -----
+@pytest.mark.parametrize("G,KP,K,want", [
+    (1, 8, 7, [[0, 6], [3, 2], [5, 0], [6, 2]]),
+    (4, 4, 14, [[0, 13], [4, 7], [10, 1], [13, 6]]),
+])
+def test_unit_draw_matches_the_inlined_draw_it_replaced(G, KP, K, want):
+    """Two hand-built units (counts and word factors below, α = 0.1, columns ≥ K zero) and four
+    pairs of Philox words. ``want``: the topics the draw gave while it was still written out in
+    gibbs_pass and in foldin_pass (the same lines in both), recorded from that code on these inputs."""
+    KS = G * KP
+    j = np.arange(KS, dtype=np.int64)
+    n = np.stack([(j * 7 + 3) % 5, (j * 3 + 1) % 4]).astype(np.int32)
+    av = (n.astype(spec.F32) + spec.F32(0.1)).reshape(2, G, KP)
+    q = np.stack([(j * 5 + 2) % 11 + 1, (j * 2 + 7) % 13 + 1]).astype(spec.F32) / spec.F32(64)
+    q[:, K:] = 0
+    words = ([0x00000000, 0xFFFFFFFF], [0x40000000, 0x9E3779B9], [0xC0000000, 0x12345678], [0xFFFFFF00, 0x80000000])
+    got = [spec.unit_draw(av, q.reshape(2, G, KP), np.array(rr, dtype=np.uint32), K).tolist() for rr in words]
+    assert got == want
