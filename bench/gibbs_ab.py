@@ -34,6 +34,7 @@ def main() -> int:
 
     from oni355 import ops
     from oni355.models.gibbs import GibbsConfig, GibbsLDA
+    from oni355.ops import CountMode
     from oni355.pipeline import common, flow
     from oni355.synth.flow import generate_flows
 
@@ -80,7 +81,7 @@ def main() -> int:
         st = {}
         md = m._sweep_mode(m.sweeps_done + 1)
         for stage in range(5):
-            if stage == 3 and md != 3:
+            if stage == 3 and md != CountMode.DUAL:
                 continue
             if stage == 4 and not m.mh:
                 continue
@@ -95,16 +96,16 @@ def main() -> int:
                         st0.update(m.mh_state())
                     ops.gibbs_pass(st0, m.G, m.KP, m.K, m.alpha, m.cfg.seed, False, m.sweep_ctr,
                                    c.chunk_len, mode=md, sampler=m.qpf, alpha_in_row=m._air,
-                                   mh_doc_moves=getattr(m, "mh_doc_moves", 1),
-                                   chg_mask=m.wbits if md == 4 else getattr(m, "chg_mask", None), wpos=c.wpos,
-                                   z_w=getattr(m, "z_w", None), zz_w=getattr(m, "zz_w", None))
-                elif stage == 1 and md == 0:
+                                   mh_doc_moves=m.mh_doc_moves,
+                                   chg_mask=m.wbits if md == CountMode.WDELTA else m.chg_mask, wpos=c.wpos,
+                                   z_w=m.z_w, zz_w=m.zz_w)
+                elif stage == 1 and md == CountMode.RECOUNT:
                     ops.recount(c.wsorted, c.wslot, m.tok_z, head, m.KS)
-                elif stage == 1 and md == 3:
+                elif stage == 1 and md == CountMode.DUAL:
                     ops.recount(c.wsorted, None, m.z_w, head, m.KS)
-                elif stage == 1 and md == 4:
+                elif stage == 1 and md == CountMode.WDELTA:
                     ops.wdelta_recount(m.wbits, c.wsorted, m.zz_w, head, m.KS)
-                elif stage == 1 and md == 2:
+                elif stage == 1 and md == CountMode.DELTA:
                     ops.delta_recount(c.wslot, c.tile_wlo, c.tile_whi, m.chg_mask, c.tok_word, m.tok_z, m.tok_zprev,
                                       head, m.KS, m.G)
                 elif stage == 3:
@@ -115,7 +116,7 @@ def main() -> int:
                     m.mh_build_tables()
                 elif stage == 2:
                     ops.gibbs_apply(m.nwk, m.dn[m.b], m.dn[1 - m.b], m.nk[m.cn], m.nk[1 - m.cn], m.q, m.qfix, m.V, m.K, m.KS,
-                                    m.beta, m.vbeta, m.sweep_ctr, bump=False, absolute=md in (0, 3))
+                                    m.beta, m.vbeta, m.sweep_ctr, bump=False, absolute=md.absolute)
                 ev[1].record()
                 torch.cuda.synchronize()
                 ts.append(ev[0].elapsed_time(ev[1]))

@@ -15,6 +15,7 @@ import torch
 from .. import ops
 from ..ref import foldin_spec
 from ..utils.obs import traced
+from .average import theta_rows
 from .corpus import Corpus
 
 
@@ -99,14 +100,7 @@ class FoldIn:
     def theta(self) -> torch.Tensor:
         """θ = (Σn_dk + S·α)/(Σn_d + S·K·α) over the S window samples, KS-padded with zeros."""
         S, K = float(max(self.samples, 1)), self.K
-        if self.device.type == "cuda":
-            return ops.theta_rows(self.ndk_sum, K, S * self.alpha, S * K * self.alpha)
-        # the float expression of GibbsLDA._averaged (CPU and GPU θ agree bit for bit)
-        n = self.ndk_sum.to(torch.float32)
-        nd = self.ndk_sum[:, :K].to(torch.int64).sum(1, keepdim=True).to(torch.float32)
-        th = (n + S * self.alpha) / (nd + S * K * self.alpha)
-        th[:, K:] = 0
-        return th.contiguous()
+        return theta_rows(self.ndk_sum, K, S * self.alpha, S * K * self.alpha)
 
     def phi(self) -> torch.Tensor:
         return self.table

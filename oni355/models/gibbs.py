@@ -23,10 +23,13 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..ops import CountMode
 from ..ref import spec
 from ..utils.obs import traced
 from ..utils import fault
+from .average import INT32_COUNT_MAX, PosteriorAverage, theta_rows
 from .corpus import Corpus, canonical_tokens
+from .x01 import X01_PACK_MIN_BYTES, X01Payload  # noqa: F401 -- X01_PACK_MIN_BYTES: this module's name for it too
 
 
 NK_REP = 32
@@ -44,11 +47,6 @@ def default_beta(K: int) -> float:
     tokens and recall collapses -- so the K = 20 / 50 models keep 0.01."""
     return 0.1 if K >= BETA_WIDE_MIN_K else 0.01
 POLL_GIVE_UP_SWEEP = 40  # auto count mode: last sweep that may still start a far-off switch
-# largest global token count a model takes: every int32 count (n_wk, n_k, n_dk, Δ) is ≤ the token
-# count, and the Δn_k replicas hold partial sums of it
-INT32_COUNT_MAX = 2**31 - 1
-# X01 payload packing pays only once the all-reduce is bandwidth-bound (see GibbsLDA._x01_wanted)
-X01_PACK_MIN_BYTES = 4 << 20
 # sweep kernels (-> oni_gibbs_launch variant argument): every one draws the same topics bit for bit
 MH_ALIAS_MAX_BYTES = 128e6  # word alias records above this size (half the MALL) use the CDF proposal
 SAMPLERS = {"generic": 0, "lds": 2, "x1": 3, "mh": ops.SAMPLER_MH}
@@ -229,9 +227,10 @@ class GibbsLDA:
             raise ValueError(f"unknown count_mode {cfg.count_mode}")
         self.auto = cfg.count_mode == "auto"
         # auto: full recount while most topics still move, then the delta mode named by auto_delta
-        auto_delta = {"wdelta": 4, "delta": 2}[cfg.auto_delta]
-        self.mode = {"recount": 0, "atomic": 1, "delta": 2, "dual": 3, "wdelta": 4, "auto": auto_delta}[cfg.count_mode]
-        # the auxiliary topic state of self.mode (z_prev for 2, word-sorted z_w for 4) matches tok_z
+        auto_delta = {"wdelta": CountMode.WDELTA, "delta": CountMode.DELTA}[cfg.auto_delta]
+        self.mode = auto_delta if self.auto else CountMode[cfg.count_mode.upper()]
+        # the auxiliary topic state of self.mode (z_prev of DELTA, the word-sorted z_w of DUAL,
+        # the empty change bitmap of WDELTA) matches tok_z
         self._aux_synced = False
         self._delta_on = False
         self._force_mode = None
@@ -239,31 +238,35 @@ class GibbsLDA:
         self._poll_off = False
         self.T_global = corpus.T
         self.change_log: list[tuple[int, float]] = []
-        # auto's early (high change rate) sweeps: "recount" (0, default) rebuilds n_wk by the
-        # gathered recount; "dual" (3) keeps a word-sorted z copy current for changed tokens so the
+        # auto's early (high change rate) sweeps: "recount" (default) rebuilds n_wk by the
+        # gathered recount; "dual" keeps a word-sorted z copy current for changed tokens so the
         # recount streams it (1 B per token) -- measured slower on the 12.5M-flow day (0.2673 ->
         # 0.2718 ms/sweep: the sampler's scattered byte stores cost more than the gather saves).
         # ONI_AUTO_EARLY overrides.
         early = os.environ.get("ONI_AUTO_EARLY", "recount")
         if early not in ("dual", "recount"):
             raise ValueError(f"unknown ONI_AUTO_EARLY {early}")
-        self.early = 3 if (self.auto and self.mode == 4 and early == "dual") else 0
+        self.early = (CountMode.DUAL if self.auto and self.mode == CountMode.WDELTA and early == "dual"
+                      else CountMode.RECOUNT)
         self._zw_synced = False  # z_w == tok_z in word-sorted order
-        if self.mode == 3 or self.early == 3:
+        # the count modes' auxiliary state, None where the model's modes do not use it
+        self.z_w = self.wbits = self.zz_w = self.tok_zprev = self.chg_mask = None
+        if CountMode.DUAL in (self.mode, self.early):
             self.z_w = torch.empty(max(corpus.T, 1), dtype=torch.uint8, device=dev)  # synced before use
-        if self.mode == 4:
+        if self.mode == CountMode.WDELTA:
             # word-sorted change bitmap (+ slack word) and per-position records: (old | new << 8) of
             # each changed token (only read where a bit is set, so never synced with tok_z) next to
             # the position's word row in its recount block (written once here)
             self.wbits = torch.empty((corpus.T + 31) // 32 + 1, dtype=torch.int32, device=dev)  # _sync_aux_z zeroes
             self.zz_w = ops.wdelta_records(corpus.wsorted)
-        if self.mode == 2:
+        if self.mode == CountMode.DELTA:
             self.tok_zprev = torch.zeros_like(self.tok_z)
             self.chg_mask = torch.zeros(max(corpus.sell_slots // corpus.S, 1), dtype=torch.int64, device=dev)
         if cfg.sampler not in SAMPLERS and cfg.sampler not in ("auto", "dense"):
             raise ValueError(f"unknown sampler {cfg.sampler}")
         samp = sampler_for(cfg.K, cfg.sampler)
         self.mh = samp == "mh"
+        self.mh_doc_moves = 1  # _setup_mh: ONI_MH_DOC_MOVES
         if samp == "dense":
             self.qpf = SAMPLERS["x1"] if self.G == 1 else SAMPLERS["lds"]
         elif self.mh:
@@ -298,6 +301,7 @@ class GibbsLDA:
         # apply adds; its count mode decides absolute / delta (_pend_abs). Every sweep() call
         # ends in a drain (_lag_drain): the counts are current between calls.
         self.lag = bool(cfg.x01_lag)
+        self.tok_zlag = self.x01_red = None
         if self.lag:
             if self.mh:
                 raise ValueError("the lagged X01 (ONI_X01_LAG) runs the dense samplers only")
@@ -318,6 +322,7 @@ class GibbsLDA:
         self.likelihoods: list[tuple[int, float]] = []
         self._graph = None
         self._graphs: dict = {}
+        self._graph_off = False  # a capture failed on some rank: eager sweeps for the rest of the model
         self._eager_lead_done = False  # the eager pair that hides a model's first capture (_sweep_n)
         self._watchdog = fault.Watchdog.from_env()
         self.timings = {"allreduce_calls": 0}
@@ -326,9 +331,9 @@ class GibbsLDA:
         self._last_inplace = False  # the last executed sweep applied in place (Δ heads untouched)
         self._corrupted = False
         self._tail_cache = None  # (sweeps_done, device tail sums, host copy): see _tail()
-        self._x01 = None
-        if comm is not None and comm.dist and self.KS % 2 == 0 and self._x01_wanted():
-            self._setup_x01()
+        self._x01 = None  # the packed X01 payload (models/x01.py), None: the Δ buffer travels as it is
+        if comm is not None and comm.dist:
+            self._x01 = X01Payload.build(self.dn[0], corpus.wsorted, self.V, self.KS, comm)
         if self.lag:
             self.x01_red = torch.zeros_like(self.dn[0])
         # one rank (no process group, or a 1-rank group whose all-reduce is the identity): the count
@@ -340,10 +345,8 @@ class GibbsLDA:
         # chunk starts (doc-local token positions) are multiples of the chunk length L, pieces of
         # split documents included: with L % 4 == 0 every chunk starts a Philox 4-token group
         self._pos_aligned = int(self.c.L) % 4 == 0
-        self._avg = None          # posterior-averaging accumulators (plan_average)
-        self._acc = False         # sweeps add their counts to the accumulators (inside graphs too)
-        self._avg_at: list = []   # sweep counts at which a sample is added
-        self._avg_cache = None    # (θ, φ) of the completed average
+        self._avg = PosteriorAverage(self.K, self.KS, self.alpha, self.beta, self.vbeta, dev)  # plan_average
+        self._acc = False         # sweeps add their counts to its sums (inside graphs too)
 
     def _make_guard(self):
         """Device exactness guard (k_exact_guard) for a corpus with documents past the range in
@@ -436,51 +439,7 @@ class GibbsLDA:
                     chunk_dslot=self.chunk_dslot, mh_lmax=self.mh_lmax)
 
     def _x01_wanted(self) -> bool:
-        """``ONI_X01_PACK``: "1" always packs, "0" never, "auto" (default) packs when the dense Δ
-        buffer is at least ``ONI_X01_PACK_MIN_BYTES`` (default 4 MiB). Below that the all-reduce
-        is latency-bound (a 0.46 MB flow-day buffer costs about the same as half of it) and the
-        pack + unpack kernels would be two extra graph nodes per sweep for nothing."""
-        mode = os.environ.get("ONI_X01_PACK", "auto")
-        if mode in ("0", "1"):
-            return mode == "1"
-        min_bytes = int(os.environ.get("ONI_X01_PACK_MIN_BYTES", str(X01_PACK_MIN_BYTES)))
-        return self.dn[0].numel() * self.dn[0].element_size() >= min_bytes
-
-    def _setup_x01(self) -> None:
-        """Packed X01 payload (csrc/kernels/x01.hip). A word's per-rank value (an absolute local
-        count in recount sweeps, a delta otherwise) is bounded by its local token count c_{w,r}, so
-        words with max_r c_{w,r} ≤ O8 = ⌊127 / W⌋ travel as four offset bytes per int32 word, words
-        up to O = ⌊32767 / W⌋ as two offset 16-bit halves, and the ring sum stays exact; the rest
-        stays int32. A realistic vocabulary is mostly rare words: 13.6 MB → ~3.4 MB per sweep at
-        V = 170k, K = 20 (dense → 8-bit)."""
-        W = self.comm.world
-        O = 32767 // W
-        O8 = 127 // W
-        if os.environ.get("ONI_X01_LIGHT_MAX"):  # tests: force a tiny/light/heavy mix on small days
-            O = min(O, int(os.environ["ONI_X01_LIGHT_MAX"]))
-        if os.environ.get("ONI_X01_TINY_MAX"):
-            O8 = min(O8, int(os.environ["ONI_X01_TINY_MAX"]))
-        O8 = min(O8, O)
-        V, KS = self.V, self.KS
-        dev = self.device
-        cnt = torch.zeros(V, dtype=torch.int64, device=dev)
-        if self.c.T:  # wsorted is sorted: run lengths by binary search, no contended histogram
-            ws = self.c.wsorted.to(torch.int64)
-            edges = torch.searchsorted(ws, torch.arange(V + 1, dtype=torch.int64, device=dev))
-            cnt += edges[1:] - edges[:-1]
-        self.comm.allreduce_(cnt, op="max")
-        if KS % 4:
-            O8 = -1  # four counts per word need KS % 4 == 0 (always true for choose_tiling)
-        tiny = torch.nonzero(cnt <= O8).flatten().to(torch.int32)
-        light = torch.nonzero((cnt > O8) & (cnt <= O)).flatten().to(torch.int32)
-        heavy = torch.nonzero(cnt > O).flatten().to(torch.int32)
-        tail_off, tail_len = V * KS, self.dn[0].numel() - V * KS
-        n = ops.x01_packed_len(tiny.numel(), light.numel(), heavy.numel(), KS, tail_len)
-        if n >= self.dn[0].numel():
-            return
-        self._x01 = dict(tiny=tiny.contiguous(), light=light.contiguous(), heavy=heavy.contiguous(), O8=max(O8, 0),
-                         O=O, WO8=W * max(O8, 0), WO=W * O, tail_off=tail_off, tail_len=tail_len,
-                         buf=torch.zeros(n, dtype=torch.int32, device=dev))
+        return X01Payload.wanted(self.dn[0])
 
     # ---------------------------------------------------------------------------------------------
     def _state(self, init: bool) -> dict:
@@ -506,16 +465,14 @@ class GibbsLDA:
         for t in (*self.ndk, self.nwk, *self.nk, *self.dn):
             t.zero_()
         self.tok_z.zero_()
-        self.a = self.b = 0
-        self.cn = 0
         # topics drawn without n_wk atomics, then n_wk rebuilt by the word-sorted recount (integer
         # counts: identical to the atomic build, without its same-address contention)
         st = self._state(True)
         if self.mh:
             st["mh_lmax"] = self.mh_lmax
         ops.gibbs_pass(st, self.G, self.KP, self.K, self.alpha, self.cfg.seed, True,
-                       self.sweep_ctr, self.c.chunk_len, host_sweep=0, mode=0,
-                       sampler=SAMPLERS["mh"] if self.mh else 0, word_init=self.cfg.init == "word")
+                       self.sweep_ctr, self.c.chunk_len, host_sweep=0, mode=CountMode.RECOUNT,
+                       sampler=SAMPLERS["mh"] if self.mh else SAMPLERS["generic"], word_init=self.cfg.init == "word")
         ops.recount(self.c.wsorted, self.c.wslot, self.tok_z, self.nwk, self.KS)
         self._split_sync_absolute(self.ndk[0])
         if self.comm is not None and self.comm.dist:
@@ -523,14 +480,19 @@ class GibbsLDA:
             self.comm.allreduce_(self.nk[0])
         # one rank (a forced 1-rank group too): every token holds one topic, so Σ n_k = T (no device
         # read, no host sync behind the init kernels); DP: the global sum
-        self.T_global = (int(self.nk[0][: self.K].sum()) if self.comm is not None and self.comm.live
-                         else int(self.c.T))
+        self._reset_chain(0, None if self.comm is not None and self.comm.live else int(self.c.T))
+
+    def _reset_chain(self, sweeps_done: int, T_global: int | None = None) -> None:
+        """The chain starts (or resumes) at ``sweeps_done`` from tok_z and the n_wk, nk[0], ndk[0] just
+        filled. ``T_global``: the global token count where the caller knows it (else Σ n_k, a device read)."""
+        self._sync_aux_z()
+        self.a = self.b = self.cn = 0
+        self.sweeps_done = sweeps_done
+        self.T_global = int(self.nk[0][: self.K].sum()) if T_global is None else T_global
         self._check_magnitude()
         self._delta_on = False
         self._chg_q = []
         self._poll_off = False
-        self._sync_aux_z()
-        self.sweeps_done = 0
         self._graph = None
         self._prime()
 
@@ -569,10 +531,10 @@ class GibbsLDA:
         r = sp["all_rows"]
         dst.index_copy_(0, r, src.index_select(0, r) + reg.index_select(0, sp["all_j"]))
 
-    def _sweep_mode(self, sweep: int) -> int:
+    def _sweep_mode(self, sweep: int) -> CountMode:
         """Count mode used by (1-based) sweep ``sweep``."""
         if self._force_mode is not None:
-            return self._force_mode
+            return CountMode(self._force_mode)
         if self.auto:
             if self.cfg.auto_switch > 0:
                 return self.early if sweep < self.cfg.auto_switch else self.mode
@@ -622,37 +584,45 @@ class GibbsLDA:
                 self._poll_off = True
                 self._chg_q.clear()
 
-    def _ensure_zw(self) -> None:
-        """Word-sorted z copy := tok_z before a dual-mode (3) sweep (eager, never captured)."""
-        if not self._zw_synced and self.c.T:
+    def _gather_zw(self) -> None:
+        """Word-sorted z copy := tok_z."""
+        if self.c.T:
             self.z_w[: self.c.T] = self.tok_z[self.c.wslot.long()]
+
+    def _ensure_zw(self) -> None:
+        """Word-sorted z copy := tok_z before a DUAL sweep (eager, never captured)."""
+        if not self._zw_synced:
+            self._gather_zw()
         self._zw_synced = True
 
     def _sync_aux_z(self) -> None:
         """Bring the auxiliary topic copies (z_prev / word-sorted z) in line with tok_z."""
-        if self.mode == 2:
+        if self.mode == CountMode.DELTA:
             self.tok_zprev.copy_(self.tok_z)
-        elif self.mode == 3 and self.c.T:
-            self.z_w[: self.c.T] = self.tok_z[self.c.wslot.long()]
-        elif self.mode == 4:
+        elif self.mode == CountMode.DUAL:
+            self._gather_zw()
+        elif self.mode == CountMode.WDELTA:
             self.wbits.zero_()
         self._aux_synced = True
 
     def _keeps_aux(self, mode: int) -> bool:
         """Does a sweep in count mode ``mode`` leave self.mode's auxiliary topic state in sync?"""
-        return mode == self.mode or self.mode == 4  # MODE 4's bitmap is empty between sweeps
+        return mode == self.mode or self.mode == CountMode.WDELTA  # its bitmap is empty between sweeps
+
+    def _apply(self, dcur: torch.Tensor, dother: torch.Tensor, **kw) -> None:
+        """ops.gibbs_apply of the Δ buffer ``dcur`` on this model's tables, nk[cn] → nk[1 − cn]; ``kw``:
+        what differs between the applies (bump, absolute, rows_copy, acc, inplace)."""
+        so = self._split_off
+        ops.gibbs_apply(self.nwk, dcur[:so], dother[:so], self.nk[self.cn], self.nk[1 - self.cn], self.q, self.qfix,
+                        self.V, self.K, self.KS, self.beta, self.vbeta, self.sweep_ctr, **kw)
 
     def _prime(self) -> None:
         # zero-delta apply: q from n_wk, nk[1] = nk[0]; leaves dn[0], dn[1] zero
         self._tail_cache = None
         self._zw_synced = False  # tok_z was (re)written outside the sweeps (init / restore)
-        VK = self.V * self.KS
         self.dn[0].zero_()
-        so = self._split_off
-        ops.gibbs_apply(self.nwk, self.dn[0][:so], self.dn[1][:so], self.nk[self.cn], self.nk[1 - self.cn], self.q,
-                        self.qfix, self.V,
-                        self.K, self.KS, self.beta, self.vbeta, self.sweep_ctr, bump=False,
-                        rows_copy=(self.ndk[self.a], self.ndk[1 - self.a], self.c.long_rows))
+        self._apply(self.dn[0], self.dn[1], bump=False,
+                    rows_copy=(self.ndk[self.a], self.ndk[1 - self.a], self.c.long_rows))
         self.cn = 1 - self.cn
         self.sweep_ctr.fill_(self.sweeps_done + 1)
         self._last_inplace = False  # dn[0] zeroed here, dn[1] by the apply
@@ -662,25 +632,24 @@ class GibbsLDA:
             self.tok_zlag.copy_(self.tok_z)
             self._pend_abs = False
             self._lag_base = self.sweeps_done
-        _ = VK
 
     # ---------------------------------------------------------------------------------------------
     def _one_sweep(self) -> None:
         c = self.c
         mode = self._sweep_mode(self.sweeps_done + 1)
-        if mode == self.mode and mode in (2, 4) and not self._aux_synced:
+        if mode == self.mode and mode in (CountMode.DELTA, CountMode.WDELTA) and not self._aux_synced:
             self._sync_aux_z()  # entering a delta mode: z_prev / z_w := z (eager, outside graphs)
         self._aux_synced = self._keeps_aux(mode)
-        if mode == 3 and not self._capturing:
+        if mode == CountMode.DUAL and not self._capturing:
             self._ensure_zw()
         # long (chunked) documents add their Δn_dk into ndk[1-a] rows that hold a copy of ndk[a]:
         # every apply -- the previous sweep's, or _prime()'s after init / resume -- seeds that copy
         st = self._state(False)
-        inplace = self._inplace_ok and mode in (1, 2, 4)
+        inplace = self._pair_inplace(mode)
         if not inplace and self._last_inplace and not self._capturing:
             self._clean_heads()
         if inplace:
-            st["dnwk"] = self.nwk  # MODE 1: the sampler's Δ atomics land in n_wk itself
+            st["dnwk"] = self.nwk  # ATOMIC: the sampler's Δ atomics land in n_wk itself
         if self.mh:
             self.mh_build_tables()
             st.update(self.mh_state())
@@ -691,20 +660,20 @@ class GibbsLDA:
             st["exact_guard"] = g["flag"]
         ops.gibbs_pass(st, self.G, self.KP, self.K, self.alpha, self.cfg.seed, False,
                        self.sweep_ctr, c.chunk_len, host_sweep=self.sweeps_done + 1, mode=mode, sampler=self.qpf,
-                       chg_mask=self.wbits if mode == 4 else getattr(self, "chg_mask", None), wpos=c.wpos,
-                       z_w=getattr(self, "z_w", None), zz_w=getattr(self, "zz_w", None), alpha_in_row=self._air,
-                       mh_doc_moves=getattr(self, "mh_doc_moves", 1), pos_aligned=self._pos_aligned)
+                       chg_mask=self.wbits if mode == CountMode.WDELTA else self.chg_mask, wpos=c.wpos,
+                       z_w=self.z_w, zz_w=self.zz_w, alpha_in_row=self._air,
+                       mh_doc_moves=self.mh_doc_moves, pos_aligned=self._pos_aligned)
         head = self.nwk if inplace else self.dn[self.b][: self.V * self.KS].view(self.V, self.KS)
-        if mode == 4:
+        if mode == CountMode.WDELTA:
             # dn[b] head := Δn_wk of the tokens marked in the word-sorted change bitmap
             ops.wdelta_recount(self.wbits, c.wsorted, self.zz_w, head, self.KS)
-        elif mode == 0:
+        elif mode == CountMode.RECOUNT:
             # dn[b] head := this rank's n_wk rebuilt from z (tail keeps Δn_k)
             ops.recount(c.wsorted, c.wslot, self.tok_z, head, self.KS)
-        elif mode == 3:
+        elif mode == CountMode.DUAL:
             # dn[b] head := this rank's n_wk, streamed from the word-sorted topic copy
             ops.recount(c.wsorted, None, self.z_w, head, self.KS)
-        elif mode == 2:
+        elif mode == CountMode.DELTA:
             # dn[b] head := Δn_wk of the tokens that changed topic this sweep
             ops.delta_recount(c.wslot, c.tile_wlo, c.tile_whi, self.chg_mask, c.tok_word, self.tok_z, self.tok_zprev,
                               head, self.KS, self.G)
@@ -718,29 +687,25 @@ class GibbsLDA:
             self._allreduce_dn(self.dn[self.b])
         if self._split is not None:
             self._split_apply(self.dn[self.b], self.ndk[self.a], self.ndk[1 - self.a])
-        so = self._split_off
         # inside a contiguous averaging window the sample sums gain this sweep's counts in the
         # same launch (int64: no extra pass over n_wk, no separate adds)
-        acc = ((self._avg["wk"], self._avg["k"], self._avg["dk"], self.ndk[1 - self.a]) if self._acc else None)
+        acc = self._avg.acc(self.ndk[1 - self.a]) if self._acc else None
+        rows_copy = (self.ndk[1 - self.a], self.ndk[self.a], c.long_rows)
         if self._lag_live:
             # join the collective; add the previous sweep's reduced Δ (absolute if that sweep
             # recounted) and zero its buffer, which the next sweep writes
             self._x01_finish(pending)
-            ops.gibbs_apply(self.nwk, self.x01_red[:so], self.dn[1 - self.b][:so], self.nk[self.cn],
-                            self.nk[1 - self.cn], self.q, self.qfix, self.V, self.K, self.KS, self.beta, self.vbeta,
-                            self.sweep_ctr, bump=True, absolute=self._pend_abs,
-                            rows_copy=(self.ndk[1 - self.a], self.ndk[self.a], c.long_rows), acc=acc)
-            self._pend_abs = mode in (0, 3)
+            self._apply(self.x01_red, self.dn[1 - self.b], bump=True, absolute=self._pend_abs, rows_copy=rows_copy,
+                        acc=acc)
+            self._pend_abs = mode.absolute
         else:
-            ops.gibbs_apply(self.nwk, self.dn[self.b][:so], self.dn[1 - self.b][:so], self.nk[self.cn],
-                            self.nk[1 - self.cn], self.q, self.qfix, self.V, self.K, self.KS, self.beta, self.vbeta,
-                            self.sweep_ctr, bump=True, absolute=mode in (0, 3),
-                            rows_copy=(self.ndk[1 - self.a], self.ndk[self.a], c.long_rows), acc=acc, inplace=inplace)
+            self._apply(self.dn[self.b], self.dn[1 - self.b], bump=True, absolute=mode.absolute, rows_copy=rows_copy,
+                        acc=acc, inplace=inplace)
         self.a, self.b, self.cn = 1 - self.a, 1 - self.b, 1 - self.cn
         self.sweeps_done += 1
         self._tail_cache = None
         if not self._capturing:
-            self._zw_synced = mode == 3
+            self._zw_synced = mode == CountMode.DUAL
             self._last_inplace = inplace
 
     def sweep_kernels(self, mode: int | None = None, lag: bool | None = None):
@@ -762,11 +727,11 @@ class GibbsLDA:
             d[:VK].zero_()
         self._last_inplace = False
 
-    def _pair_inplace(self, mode: int) -> bool:
-        return self._inplace_ok and mode in (1, 2, 4)
+    def _pair_inplace(self, mode: CountMode) -> bool:
+        return self._inplace_ok and mode.in_place
 
-    def _lag_due(self, sweep: int, mode: int) -> bool:
-        """Does (1-based) sweep ``sweep`` (of count mode ``mode``) run with the lagged X01?"""
+    def _lag_due(self, sweep: int) -> bool:
+        """Does (1-based) sweep ``sweep`` run with the lagged X01?"""
         return self.lag and sweep >= self._lag_from
 
     def _lag_enter(self) -> None:
@@ -785,15 +750,11 @@ class GibbsLDA:
         cannot read and zero one buffer) runs on the compute stream; the collective is issued
         asynchronously, so RCCL runs it on its own stream while this sweep's sampler runs, and
         :meth:`_x01_finish` joins it before the apply -- inside the captured sweep graph too."""
-        so = self._split_off
-        x = self._x01
-        if x is not None:
-            ops.x01_pack(src, x["tiny"], x["light"], x["heavy"], self.KS, x["tail_off"], x["tail_len"], x["O8"],
-                         x["O"], x["buf"])
-            buf = x["buf"]
+        buf = self._traveller(self.x01_red[: self._split_off])
+        if self._x01 is not None:
+            self._x01.pack(src)
         else:
-            self.x01_red[:so].copy_(src[:so])
-            buf = self.x01_red[:so]
+            buf.copy_(src[: self._split_off])
         # (no timing events: issue → join spans the sampler; allreduce_ms_per_sweep probes the
         # payload's collective on its own instead)
         h = self.comm.allreduce_async_(buf) if self.comm is not None else None
@@ -804,21 +765,16 @@ class GibbsLDA:
     def _x01_finish(self, h) -> None:
         if h is not None:
             h.wait()
-        x = self._x01
-        if x is not None:
-            ops.x01_unpack(x["buf"], x["tiny"], x["light"], x["heavy"], self.KS, x["tail_off"], x["tail_len"],
-                           x["WO8"], x["WO"], self.x01_red)
+        if self._x01 is not None:
+            self._x01.unpack(self.x01_red)
 
     def _lag_drain(self) -> None:
         """End of a sweep() call with the lagged X01: reduce and add the last sweep's Δ (no sample
         is drawn and the sweep counter stays), so n_wk, n_k and q are current again; the next
         sweep's word side then counts every token at tok_z."""
         pb = 1 - self.b
-        so = self._split_off
         self._x01_finish(self._x01_start(self.dn[pb]))
-        ops.gibbs_apply(self.nwk, self.x01_red[:so], self.dn[pb][:so], self.nk[self.cn], self.nk[1 - self.cn], self.q,
-                        self.qfix, self.V, self.K, self.KS, self.beta, self.vbeta, self.sweep_ctr, bump=False,
-                        absolute=self._pend_abs)
+        self._apply(self.x01_red, self.dn[pb], bump=False, absolute=self._pend_abs)
         # n_k back into the current slot: the sweep parities (a, b, cn) keep their relation, so the
         # captured sweep pairs replay after the drain
         self.nk[self.cn].copy_(self.nk[1 - self.cn])
@@ -826,7 +782,11 @@ class GibbsLDA:
         self._pend_abs = False
         self._lag_base = self.sweeps_done  # the next sweep reduces the zeroed buffer: no count
         self._tail_cache = None
-        self._avg_cache = None
+        self._avg.cache = None
+
+    def _traveller(self, dn: torch.Tensor) -> torch.Tensor:
+        """The buffer the X01 all-reduce sums for the Δ buffer ``dn``: the packed payload's, else ``dn``."""
+        return self._x01.buf if self._x01 is not None else dn
 
     def _allreduce_dn(self, buf: torch.Tensor) -> None:
         """X01: all-reduce of the sweep's Δ buffer (Δn_wk ‖ Δn_k replicas ‖ aux words).
@@ -839,20 +799,15 @@ class GibbsLDA:
         if timed:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
-        x = self._x01
         # a forced 1-rank group (ONI_FORCE_DIST=1: every data-parallel code path on one GPU) keeps
         # the pack / unpack but drops the collective itself -- the sum over one rank is the identity
         # -- unless ONI_COMM_REAL=1 (comm.live), which runs the RCCL all-reduce inside the graph
-        reduce = self.comm.live
-        if x is not None:
-            ops.x01_pack(buf, x["tiny"], x["light"], x["heavy"], self.KS, x["tail_off"], x["tail_len"], x["O8"], x["O"],
-                         x["buf"])
-            if reduce:
-                self.comm.allreduce_(x["buf"])
-            ops.x01_unpack(x["buf"], x["tiny"], x["light"], x["heavy"], self.KS, x["tail_off"], x["tail_len"], x["WO8"],
-                           x["WO"], buf)
-        elif reduce:
-            self.comm.allreduce_(buf)
+        if self._x01 is not None:
+            self._x01.pack(buf)
+        if self.comm.live:
+            self.comm.allreduce_(self._traveller(buf))
+        if self._x01 is not None:
+            self._x01.unpack(buf)
         if timed:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
@@ -863,7 +818,7 @@ class GibbsLDA:
         """Bytes each rank contributes to X01 per sweep (0 without a process group)."""
         if self.comm is None or not self.comm.dist:
             return 0
-        b = self._x01["buf"] if self._x01 is not None else self.dn[0]
+        b = self._traveller(self.dn[0])
         return int(b.numel() * b.element_size())
 
     def allreduce_ms_per_sweep(self, probe_reps: int = 20) -> float | None:
@@ -872,25 +827,21 @@ class GibbsLDA:
         buffer of the same size. None without a process group or off-GPU."""
         if self.comm is None or not self.comm.dist or self.device.type != "cuda":
             return None
-        times = []
-        if self._ar_events:
-            self._ar_events[-1][1].synchronize()
-            times = [a.elapsed_time(b) for a, b in self._ar_events]
-        if not times:
-            scratch = torch.zeros_like(self._x01["buf"] if self._x01 is not None else self.dn[0])
+        evs = list(self._ar_events)
+        if not evs:
+            scratch = torch.zeros_like(self._traveller(self.dn[0]))
             for _ in range(probe_reps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 self.comm.allreduce_(scratch)
                 e1.record()
-                times.append((e0, e1))
-            times[-1][1].synchronize()
-            times = [a.elapsed_time(b) for a, b in times]
-        return round(float(np.median(times)), 4)
+                evs.append((e0, e1))
+        evs[-1][1].synchronize()
+        return round(float(np.median([a.elapsed_time(b) for a, b in evs])), 4)
 
     def _graphable(self) -> bool:
-        if getattr(self, "_graph_off", False):
-            return False  # a capture failed on some rank: eager sweeps for the rest of the model
+        if self._graph_off:
+            return False
         if not (self.cfg.use_graph and self.device.type == "cuda" and os.environ.get("ONI_NO_GRAPH", "0") != "1"):
             return False
         if self.comm is None or not self.comm.dist:
@@ -985,19 +936,19 @@ class GibbsLDA:
             self._watchdog.arm()
         try:
             while n > 0:
-                nxt = [p for p in self._avg_at if p > self.sweeps_done]
-                contiguous = self._avg is not None and int(self.cfg.post_every) == 1
+                avg = self._avg
+                nxt = [p for p in avg.at if p > self.sweeps_done]
+                contiguous = bool(avg.at) and int(self.cfg.post_every) == 1
                 if nxt and contiguous and self.sweeps_done + 1 >= nxt[0]:
                     # inside a contiguous window: every sweep adds its sample, in the graph
                     self._ensure_avg()
-                    seg = min(n, self._avg_at[-1] - self.sweeps_done)
+                    seg = min(n, avg.at[-1] - self.sweeps_done)
                     self._acc = True
                     try:
                         self._sweep_n(seg)
                     finally:
                         self._acc = False
-                    self._avg["n"] += seg
-                    self._avg_cache = None
+                    avg.n, avg.cache = avg.n + seg, None
                     n -= seg
                     continue
                 if nxt and contiguous:
@@ -1006,8 +957,9 @@ class GibbsLDA:
                     seg = min(n, nxt[0] - self.sweeps_done) if nxt else n
                 self._sweep_n(seg)
                 n -= seg
-                if not contiguous and self._avg is not None and self.sweeps_done in self._avg_at:
-                    self._add_sample()
+                if not contiguous and self.sweeps_done in avg.at:
+                    self._accumulate()
+                    avg.n, avg.cache = avg.n + 1, None
             if self._lag_live:
                 self._lag_drain()
         finally:
@@ -1038,16 +990,13 @@ class GibbsLDA:
             if self.c.D > self.c.D_own:  # split-document pieces: rows past D_own
                 extra = bool((self.ndk_cur[self.c.D_own: self.c.D, :K] < 0).any())
             flags = [t[4] > 0, t[5] > 0, t[6] > 0 or extra]
-            if any(flags):
-                raise fault.NumericalFault(f"corrupt model state after sweep {self.sweeps_done}: non-finite "
-                                           f"q={flags[0]}, negative counts={flags[1] or flags[2]}")
-            return
-        flags = torch.stack([
-            (~torch.isfinite(self.q[:, :K])).any(),
-            (self.nk_cur[:K] < 0).any() | (self.nwk[:, :K] < 0).any(),
-            (self.ndk_cur[: self.c.D, :K] < 0).any() if self.c.D else torch.zeros((), dtype=torch.bool,
-                                                                                   device=self.device),
-        ]).cpu().tolist()
+        else:
+            flags = torch.stack([
+                (~torch.isfinite(self.q[:, :K])).any(),
+                (self.nk_cur[:K] < 0).any() | (self.nwk[:, :K] < 0).any(),
+                (self.ndk_cur[: self.c.D, :K] < 0).any() if self.c.D else torch.zeros((), dtype=torch.bool,
+                                                                                       device=self.device),
+            ]).cpu().tolist()
         if any(flags):
             raise fault.NumericalFault(f"corrupt model state after sweep {self.sweeps_done}: non-finite q={flags[0]}, "
                                        f"negative counts={flags[1] or flags[2]}")
@@ -1089,20 +1038,20 @@ class GibbsLDA:
             self._decide_mode()
             m1 = self._sweep_mode(self.sweeps_done + 1)
             m2 = self._sweep_mode(self.sweeps_done + 2)
-            if not self._lag_live and self._lag_due(self.sweeps_done + 1, m1):
+            if not self._lag_live and self._lag_due(self.sweeps_done + 1):
                 self._lag_enter()
             # a lagged pair's first apply adds the previous sweep's Δ: same absoluteness as m1's
             # (and a pair never straddles the start of the lag)
-            lag_off = self.lag and (self._lag_due(self.sweeps_done + 1, m1) != self._lag_due(self.sweeps_done + 2, m2)
-                                    or (self._lag_live and self._pend_abs != (m1 in (0, 3))))
+            lag_off = self.lag and (self._lag_due(self.sweeps_done + 1) != self._lag_due(self.sweeps_done + 2)
+                                    or (self._lag_live and self._pend_abs != m1.absolute))
             if not (self._graphable() and n - done >= 2 and m1 == m2) or lag_off:
                 self._one_sweep()
                 self._note_changes()
                 done += 1
                 continue
-            if m1 == self.mode and m1 in (2, 4) and not self._aux_synced:
+            if m1 == self.mode and m1 in (CountMode.DELTA, CountMode.WDELTA) and not self._aux_synced:
                 self._sync_aux_z()
-            if m1 == 3:
+            if m1 == CountMode.DUAL:
                 self._ensure_zw()
             entry = self._graphs.get((m1, self._acc, self._lag_live))
             if entry is not None and entry[1] != (self.a, self.b, self.cn):
@@ -1134,127 +1083,47 @@ class GibbsLDA:
             entry[0].replay()
             self._last_inplace = self._pair_inplace(m1)
             if self._lag_live:
-                self._pend_abs = m1 in (0, 3)
+                self._pend_abs = m1.absolute
             self.timings["graph_replays"] = self.timings.get("graph_replays", 0) + 1
             self.sweeps_done += 2
             self._aux_synced = self._keeps_aux(m1)
-            self._zw_synced = m1 == 3
+            self._zw_synced = m1 == CountMode.DUAL
             self._note_changes()
             done += 2
             if self._watchdog is not None:
                 self._watchdog.kick()
 
-    # ---- posterior averaging -------------------------------------------------------------------
+    # ---- posterior averaging (models/average.py) ------------------------------------------------
     def plan_average(self, total_sweeps: int) -> None:
-        """Average the counts of the samples at sweeps total, total - e, …, total - (S-1)·e
-        (e = cfg.post_every, S = cfg.post_samples capped at total / 4e)."""
-        S, e = max(1, int(self.cfg.post_samples)), max(1, int(self.cfg.post_every))
-        # at most the last quarter of the chain (burn-in first): a 200-sweep day averages the 50
-        # samples of sweeps 151-200, a 30-sweep run 7, a run of < 8 sweeps none. ONI_POST_SPAN
-        # (default 0.25) sets that fraction.
-        span = float(os.environ.get("ONI_POST_SPAN", "0.25"))
-        S = min(S, int(int(total_sweeps) * span) // e)
-        at = [total_sweeps - j * e for j in range(S) if total_sweeps - j * e > 0]
-        self._avg_at = sorted(at) if S > 1 else []
-        self._avg_cache = None
-        dev = self.device
-        # the sums are allocated at the first sample (_ensure_avg), when the counts they bound exist
-        self._avg = dict(n=0, wk=None, k=None, dk=None) if self._avg_at else None
-        _ = dev
+        self._avg.plan(total_sweeps, self.cfg.post_samples, self.cfg.post_every)
+
+    _avg_at = property(lambda self: self._avg.at)  # the schedule and the cache by their earlier names
+    _avg_cache = property(lambda self: self._avg.cache, lambda self, v: setattr(self._avg, "cache", v))
 
     def _ensure_avg(self) -> None:
-        """Allocate the sample sums. S samples of an int32 count wrap an int32 sum once the count
-        passes 2^31 / S (43M at S = 50: one topic's share of a config-4/5 corpus), so each table is
-        int64 when S times its largest possible entry could pass 2^31 -- n_k: the global token
-        count; n_wk: the largest global word count; n_dk: the longest document row -- and int32
-        otherwise (the default day: half the bytes in k_apply's fused add). ONI_POST_WIDE=1 forces
-        int64."""
-        a = self._avg
-        if a is None or a["wk"] is not None:
-            return
-        S, K, dev = len(self._avg_at), self.K, self.device
-        force = os.environ.get("ONI_POST_WIDE", "0") == "1"
-        wk_max = int(self.nwk[:, :K].sum(1, dtype=torch.int64).max()) if self.nwk.shape[0] else 0
-        dk_max = int(self.ndk_cur[:, :K].sum(1, dtype=torch.int64).max()) if self.c.D else 0
-
-        def dt(bound: int):
-            return torch.int64 if force or bound * S > INT32_COUNT_MAX else torch.int32
-        a["wk"] = torch.zeros(self.nwk.shape, dtype=dt(wk_max), device=dev)
-        a["k"] = torch.zeros(self.nk[0].shape, dtype=dt(max(self.T_global, int(self.nk_cur[:K].max()))), device=dev)
-        a["dk"] = torch.zeros(self.ndk[0].shape, dtype=dt(dk_max), device=dev)
+        self._avg.ensure(self.nwk, self.nk_cur, self.ndk_cur, self.T_global)
 
     @property
     def average_window(self) -> tuple[int, int] | None:
         """(first, last) sample sweep of the planned average, or None."""
-        return (self._avg_at[0], self._avg_at[-1]) if self._avg_at else None
+        return (self._avg.at[0], self._avg.at[-1]) if self._avg.at else None
 
     def average_state(self) -> dict | None:
-        """The accumulated samples (for a checkpoint; the K real topics only, so the state does
-        not depend on the kernel tiling's padding), or None outside an averaging window."""
-        a = self._avg
-        if a is None or a["n"] == 0:
-            return None
-        K = self.K
-        return {"n": int(a["n"]), "wk": a["wk"][:, :K].cpu().to(torch.int64), "k": a["k"][:K].cpu().to(torch.int64),
-                "dk": a["dk"][:, :K].cpu().to(torch.int64)}
+        """The accumulated samples (for a checkpoint), or None outside an averaging window."""
+        return self._avg.state()
 
     def load_average_state(self, st: dict) -> None:
-        """Restore :meth:`average_state` (same documents and vocabulary) after a resume inside the
-        window."""
-        a = self._avg
-        if a is None:
+        """Restore :meth:`average_state` (same documents and vocabulary) after a resume in the window."""
+        if not self._avg.at:
             raise ValueError("checkpoint holds posterior-averaging samples but no average is planned")
         self._ensure_avg()
-        K = self.K
-        for k in ("wk", "k", "dk"):
-            want = (a[k].shape[0], K) if a[k].dim() == 2 else (K,)
-            v = st[k]
-            # states saved before the K-column format hold the KS-wide tiling-padded tables (the
-            # padding topics are never used): their first K columns are the same sums
-            if tuple(v.shape[:-1]) == want[:-1] and v.shape[-1] == self.KS and self.KS != K:
-                v = v[..., :K]
-            if tuple(v.shape) != want:
-                raise ValueError(f"averaging state {k} shape {tuple(st[k].shape)} != {want}")
-            a[k].zero_()
-            a[k][..., :K].copy_(v.to(a[k].device))
-        a["n"] = int(st["n"])
-        self._avg_cache = None
+        self._avg.load_state(st)
 
     def _accumulate(self) -> None:
-        """Add the current counts to the (int64) sample sums: samples taken every post_every > 1
-        sweeps, outside the graphs (contiguous windows add inside k_apply)."""
-        self._ensure_avg()
-        a = self._avg
-        a["wk"] += self.nwk
-        a["k"] += self.nk_cur
-        a["dk"] += self.ndk_cur
-
-    def _add_sample(self) -> None:
-        self._accumulate()
-        self._avg["n"] += 1
-        self._avg_cache = None
+        self._avg.accumulate(self.nwk, self.nk_cur, self.ndk_cur, self.T_global)
 
     def _averaged(self):
-        """(θ, φ) from the accumulated samples, once every planned sample is in; else None."""
-        a = self._avg
-        if a is None or a["n"] == 0 or a["n"] != len(self._avg_at) or self.sweeps_done != self._avg_at[-1]:
-            return None
-        if self._avg_cache is None and self.device.type == "cuda":
-            S, K = float(a["n"]), self.K
-            th = ops.theta_rows(a["dk"], K, S * self.alpha, S * K * self.alpha)
-            ph = ops.phi_rows(a["wk"], a["k"], K, S * self.beta, float(np.float32(S) * np.float32(self.vbeta)))
-            self._avg_cache = (th, ph)
-        if self._avg_cache is None:
-            S, K = float(a["n"]), self.K
-            n = a["dk"].to(torch.float32)
-            nd = a["dk"][:, :K].to(torch.int64).sum(1, keepdim=True).to(torch.float32)  # as k_theta_rows
-            th = (n + S * self.alpha) / (nd + S * K * self.alpha)
-            th[:, K:] = 0
-            den = a["k"].to(torch.float32) + np.float32(S) * self.vbeta
-            ph = (a["wk"].to(torch.float32) + S * self.beta) / den
-            ph[:, K:] = 0
-            self._avg_cache = (th.contiguous(), ph.contiguous())
-        return self._avg_cache
+        return self._avg.estimate(self.sweeps_done)
 
     # ---------------------------------------------------------------------------------------------
     @property
@@ -1271,13 +1140,7 @@ class GibbsLDA:
         avg = self._averaged()
         if avg is not None:
             return avg[0]
-        if self.device.type == "cuda":
-            return ops.theta_rows(self.ndk_cur, self.K, self.alpha, self.K * self.alpha)
-        n = self.ndk_cur.to(torch.float32)
-        nd = self.ndk_cur[:, : self.K].to(torch.int64).sum(1, keepdim=True).to(torch.float32)
-        th = (n + self.alpha) / (nd + self.K * self.alpha)
-        th[:, self.K:] = 0
-        return th.contiguous()
+        return theta_rows(self.ndk_cur, self.K, self.alpha, self.K * self.alpha)
 
     def phi(self) -> torch.Tensor:
         """φ[w,k] = (n_wk+β)/(n_k+Vβ) for the current counts (= the q table), KS-padded; from the
@@ -1368,13 +1231,4 @@ class GibbsLDA:
             if self.comm is not None and self.comm.dist:
                 self.comm.allreduce_(self.nwk)
                 self.comm.allreduce_(self.nk[0])
-        self._sync_aux_z()
-        self.a = self.b = self.cn = 0
-        self.sweeps_done = sweeps_done
-        self.T_global = int(self.nk[0][: self.K].sum())
-        self._check_magnitude()
-        self._delta_on = False
-        self._chg_q = []
-        self._poll_off = False
-        self._graph = None
-        self._prime()
+        self._reset_chain(sweeps_done)

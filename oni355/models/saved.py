@@ -18,15 +18,15 @@ _ARRAYS = ("vocab", "phi", "phi_oov", "cuts_time", "cuts_ibyt", "cuts_ipkt")
 
 def oov_row(model) -> np.ndarray:
     """φ of a word with zero count under the estimate ``model.phi()`` returns: β/(n_k + Vβ) from
-    the averaged sums with their S-scaling (GibbsLDA._averaged / k_phi_rows: (0 + S·β)/(Σn_k + S·Vβ))
+    the averaged sums with their S-scaling (PosteriorAverage.estimate / k_phi_rows: (0 + S·β)/(Σn_k + S·Vβ))
     once the window is complete, else from the current n_k (the q table's expression). f32 [K]."""
     K = model.K
     f32 = np.float32
     if model._averaged() is not None:
         a = model._avg
-        S = float(a["n"])
+        S = float(a.n)
         num = f32(0) + f32(S * model.beta)
-        den = a["k"][:K].cpu().numpy().astype(f32) + f32(f32(S) * f32(model.vbeta))
+        den = a.k[:K].cpu().numpy().astype(f32) + f32(f32(S) * f32(model.vbeta))
     else:
         num = f32(0) + f32(model.beta)
         den = model.nk_cur[:K].cpu().numpy().astype(f32) + f32(model.vbeta)

@@ -12,6 +12,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
+import enum
 from typing import NamedTuple
 
 import numpy as np
@@ -22,7 +23,7 @@ from . import _lib
 
 __all__ = [
     "f32_keys", "i64_keys", "quantile_cuts", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
-    "sell_perm_z", "gibbs_pass", "foldin_pass", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "copy_rows", "score", "select_below", "choose_tiling",
+    "sell_perm_z", "gibbs_pass", "foldin_pass", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "CountMode", "copy_rows", "score", "select_below", "choose_tiling",
 ]
 
 
@@ -384,8 +385,21 @@ def sell_perm_z(chunk_doc, chunk_pos0, chunk_len, S, slice_off, doc_tok_ptr, tok
 SAMPLER_MH = 4
 
 
+class CountMode(enum.IntEnum):
+    """How a sweep keeps n_wk: the ``mode`` of :func:`gibbs_pass` (described there), an int wherever it flows."""
+    RECOUNT, ATOMIC, DELTA, DUAL, WDELTA = 0, 1, 2, 3, 4
+
+    @property
+    def absolute(self) -> bool:  # the sweep's Δ head holds this rank's n_wk itself, not a difference
+        return self in (CountMode.RECOUNT, CountMode.DUAL)
+
+    @property
+    def in_place(self) -> bool:  # the sweep's Δn_wk may be added straight into n_wk (one rank, no X01)
+        return self in (CountMode.ATOMIC, CountMode.DELTA, CountMode.WDELTA)
+
+
 def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init: bool, sweep_ctr: torch.Tensor,
-               chunk_len: torch.Tensor, host_sweep: int | None = None, mode: int = 1,
+               chunk_len: torch.Tensor, host_sweep: int | None = None, mode: int = CountMode.ATOMIC,
                sampler: int = 0, chg_mask: torch.Tensor | None = None, wpos: torch.Tensor | None = None,
                z_w: torch.Tensor | None = None, zz_w: torch.Tensor | None = None,
                alpha_in_row: bool = False, mh_doc_moves: int = 1, word_init: bool = False,
@@ -420,17 +434,17 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
         raise ValueError("dnk must hold a power-of-two number of [KS] replicas")
     if not init and (st.get("qfix") is None or st["qfix"].numel() != 2 * KS):
         raise ValueError("a sweep needs the [2, KS] token-exclusion table qfix")
-    if mode == 4:
+    if mode == CountMode.WDELTA:
         T = int(zz_w.numel()) if zz_w is not None else 0
         if (wpos is None or zz_w is None or chg_mask is None or wpos.numel() != st["tok_word"].numel()
                 or zz_w.dtype != torch.int32 or chg_mask.dtype != torch.int32 or chg_mask.numel() * 32 < T):
             raise ValueError("wdelta mode needs wpos [SELL slots], int32 zz_w [T] and an int32 bitmap of T bits")
     if not _is_dev(st["tok_word"]):
         chg = st.get("chg_count")
-        z_before = st["tok_z"].clone() if (chg is not None or mode == 4) else None
+        z_before = st["tok_z"].clone() if (chg is not None or mode == CountMode.WDELTA) else None
         npst = _np_state(st, ("tok_word", "chunk_key", "walias", "dalias"))
         npst["dnk"] = npst["dnk"][:KS]  # replica 0 (the sum over replicas is what counts)
-        if mode != 1:
+        if mode != CountMode.ATOMIC:
             npst["dnwk"] = np.zeros_like(npst["dnwk"])  # discarded: recount rebuilds n_wk
         if not init:
             npst["qfix"] = npst["qfix"].reshape(2, KS)
@@ -443,10 +457,10 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
             spec.gibbs_pass_mh(npst, KS, K, alpha, s0, s1, sweep_no, chunk_len.numpy(), doc_moves=mh_doc_moves)
         else:
             spec.gibbs_pass(npst, G, KP, K, alpha, s0, s1, init, sweep_no, chunk_len.numpy(), word_init=word_init)
-        if mode == 3:
+        if mode == CountMode.DUAL:
             valid = wpos >= 0
             z_w[wpos[valid].long()] = st["tok_z"][valid]
-        if mode == 4:
+        if mode == CountMode.WDELTA:
             ch = st["tok_z"] != z_before
             p = wpos[ch].long()
             zz16 = (z_before[ch].to(torch.int32) | (st["tok_z"][ch].to(torch.int32) << 8))
@@ -463,15 +477,15 @@ def gibbs_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init:
     if not init:
         a.qfix = _lib.ptr(st["qfix"])
     a.sweep_ctr = _lib.ptr(sweep_ctr)
-    if mode == 2:
+    if mode == CountMode.DELTA:
         if chg_mask is None or chg_mask.numel() * (64 // G) < st["tok_word"].numel():
             raise ValueError("delta mode needs a change mask with one word per SELL step")
         a.chg_mask = _lib.ptr(chg_mask)
-    if mode == 3:
+    if mode == CountMode.DUAL:
         if wpos is None or z_w is None or wpos.numel() != st["tok_word"].numel():
             raise ValueError("dual mode needs wpos [SELL slots] and z_w [T]")
         a.wpos, a.z_w = _lib.ptr(wpos), _lib.ptr(z_w)
-    if mode == 4:
+    if mode == CountMode.WDELTA:
         a.wpos, a.zz_w, a.chg_mask = _lib.ptr(wpos), _lib.ptr(zz_w), _lib.ptr(chg_mask)
     if st.get("chg_count") is not None:
         a.chg_count = _lib.ptr(st["chg_count"])

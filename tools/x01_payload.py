@@ -2,7 +2,7 @@
 """X01 payload of a W-rank day, measured on one GPU: generate the W weak-scaled shards (12.5M flows
 each, the bench's per-GPU share; --wide = the realistic-vocabulary day), wordify each with shard 0's
 cuts, take every word's maximum local token count over the shards, classify the words as the
-sampler does (models/gibbs.py _setup_x01: tiny ≤ ⌊127/W⌋, light ≤ ⌊32767/W⌋, else heavy) and report
+sampler does (models/x01.py X01Payload.build: tiny ≤ ⌊127/W⌋, light ≤ ⌊32767/W⌋, else heavy) and report
 the packed vs dense per-sweep payload.
 
   python tools/x01_payload.py --wide --worlds 2,4,8
