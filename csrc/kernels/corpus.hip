@@ -464,6 +464,157 @@ ONI_API int oni_pair_build(const int32_t* doc, const int32_t* word, const int32_
 }
 
 // ------------------------------------------------------------------------------------------------
+// doc_pair_build: dict_encode(doc keys, 32 bits) + pair_build(ids, word) of one rank's tokens in
+// ONE doc-and-pair sort. The two-call form sorts the tokens by doc key, scatters the ids back to
+// token order, and sorts the same tokens by doc·V + word again; nothing but the second sort reads
+// the ids. Here one stable sort from an iota over the composite key (doc key << word bits) | word
+// leaves the tokens in (doc key, word, position) order: the doc runs are the dictionary, the
+// (doc, word) runs the pairs, and the permutation is bit for bit the one the two-call form's pair
+// sort gave (doc ranks order as doc keys do), so tok_pair and order0 are unchanged. A pass moves
+// 12 B per token instead of 8, but both fields sit in the sorted key: no gather of doc keys or
+// words through a permutation (a random 4-B gather of 25M tokens costs 0.45-0.5 ms, 2.5 passes).
+// One packed scan (doc heads in the high word, pair heads in the low) ranks both kinds of run.
+// Outputs as oni_dict_encode (uniq, n_uniq; no token-order ids) and oni_pair_build.
+//
+// Doc keys: token p's key is a[p] for p < na, else b[p - na] (flows: the source and destination
+// address columns, no concatenated copy), each u32 bits (key_bytes 4) or an int64 whose low 32
+// bits count (key_bytes 8: narrowed as the composite key is formed, no pass of its own).
+namespace {
+
+template <class KT>
+__global__ void k_dp_keys(const KT* __restrict__ a, int64_t na, const KT* __restrict__ b,
+                          const int32_t* __restrict__ word, int64_t n, int wbits, uint64_t* __restrict__ key,
+                          int32_t* __restrict__ iota) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t d = (uint32_t)(i < na ? a[i] : b[i - na]);
+  key[i] = ((uint64_t)d << wbits) | (uint64_t)(uint32_t)word[i];
+  iota[i] = (int32_t)i;
+}
+
+// packed head flags: a doc head is also a pair head
+__global__ void k_dp_heads(const uint64_t* __restrict__ ks, int64_t n, int wbits, uint64_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t cur = ks[i], prev = i > 0 ? ks[i - 1] : 0;
+  const bool dh = i == 0 || (cur >> wbits) != (prev >> wbits);
+  const bool ph = i == 0 || cur != prev;
+  flag[i] = ((uint64_t)(dh ? 1 : 0) << 32) | (uint64_t)(ph ? 1 : 0);
+}
+
+template <bool SEQ>
+__global__ void k_dp_scatter(const uint64_t* __restrict__ ks, const int32_t* __restrict__ perm,
+                             const uint64_t* __restrict__ run, int64_t n, int wbits, uint64_t* __restrict__ uniq,
+                             int64_t* __restrict__ n_uniq, int32_t* __restrict__ pair_doc,
+                             int32_t* __restrict__ pair_word, int64_t* __restrict__ head_pos,
+                             int32_t* __restrict__ tok_pair, int64_t* __restrict__ nnz) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t cur = run[i], prev = i > 0 ? run[i - 1] : 0;
+  const int32_t r = (int32_t)(uint32_t)cur - 1;  // pair rank
+  const int32_t d = (int32_t)(cur >> 32) - 1;    // doc rank
+  if constexpr (SEQ) tok_pair[i] = r;  // sorted order: window_pass + k_scatter restore the token order
+  else tok_pair[perm[i]] = r;
+  if ((uint32_t)cur != (uint32_t)prev) {
+    const uint64_t k = ks[i];
+    pair_doc[r] = d;
+    pair_word[r] = (int32_t)(k & ((uint64_t(1) << wbits) - 1));
+    head_pos[r] = i;
+    if ((cur >> 32) != (prev >> 32)) uniq[d] = k >> wbits;
+  }
+  if (i == n - 1) {
+    *nnz = (int64_t)r + 1;
+    *n_uniq = (int64_t)d + 1;
+    head_pos[r + 1] = n;
+  }
+}
+
+}  // namespace
+
+template <class KT>
+static int doc_pair_build_impl(const KT* ka, int64_t na, const KT* kb, const int32_t* word, const int32_t* weight,
+                               int64_t n, int64_t V, uint64_t* uniq, int64_t* n_uniq, int32_t* pair_doc,
+                               int32_t* pair_word, int32_t* pair_cnt, int32_t* tok_pair, int64_t* nnz,
+                               int32_t* order0, int64_t n0, void* tmp, size_t* tmp_bytes, hipStream_t s) {
+  const int wbits = V > 1 ? bits_for((uint64_t)(V - 1)) : 0;  // V = 1: every word is 0
+  const bool back = n >= kSortBackMin;
+  const bool sel = order0 && n0 > 0;
+  Arena ar{static_cast<char*>(tmp)};
+  uint64_t* key = ar.take<uint64_t>(n);  // later: tok_pair in sorted order [n] + the window pass's values [n]
+  uint64_t* ks = ar.take<uint64_t>(n);
+  int32_t* iota = ar.take<int32_t>(n);   // later: the window pass's sorted destinations
+  int32_t* perm = ar.take<int32_t>(n);
+  uint64_t* flag = ar.take<uint64_t>(n);
+  uint64_t* run = ar.take<uint64_t>(n);
+  int64_t* head = ar.take<int64_t>(n + 1);
+  int64_t* ws = weight ? ar.take<int64_t>(n) : nullptr;
+  int64_t* psum = weight ? ar.take<int64_t>(n) : nullptr;
+  int64_t* nsel = ar.take<int64_t>(1);
+  int32_t* seq = reinterpret_cast<int32_t*>(key);
+  int32_t* wval = seq + n;
+  size_t b1 = 0, b2 = 0, b3 = 0, b4 = 0, b5 = 0;
+  ONI_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, key, ks, iota, perm, (int)n, 0, 32 + wbits, s));
+  ONI_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b2, flag, run, (int)n, s));
+  if (weight) ONI_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b3, ws, psum, (int)n, s));
+  if (sel) ONI_TRY(hipcub::DeviceSelect::If(nullptr, b4, perm, order0, nsel, (int)n, BelowN{(int32_t)n0}, s));
+  if (back) ONI_TRY(window_pass(nullptr, b5, perm, iota, seq, wval, n, s));
+  size_t cbytes = b1;
+  if (b2 > cbytes) cbytes = b2;
+  if (b3 > cbytes) cbytes = b3;
+  if (b4 > cbytes) cbytes = b4;
+  if (b5 > cbytes) cbytes = b5;
+  void* cub = ar.take<char>(cbytes);
+  if (!tmp) {
+    *tmp_bytes = ar.used + 256;
+    return 0;
+  }
+  if (n == 0) {
+    ONI_TRY(hipMemsetAsync(nnz, 0, sizeof(int64_t), s));
+    ONI_TRY(hipMemsetAsync(n_uniq, 0, sizeof(int64_t), s));
+    return (int)hipGetLastError();
+  }
+  k_dp_keys<KT><<<nblk(n), kB, 0, s>>>(ka, na, kb, word, n, wbits, key, iota);
+  ONI_TRY(hipcub::DeviceRadixSort::SortPairs(cub, cbytes, key, ks, iota, perm, (int)n, 0, 32 + wbits, s));
+  k_dp_heads<<<nblk(n), kB, 0, s>>>(ks, n, wbits, flag);
+  ONI_TRY(hipcub::DeviceScan::InclusiveSum(cub, cbytes, flag, run, (int)n, s));
+  if (back) {
+    k_dp_scatter<true><<<nblk(n), kB, 0, s>>>(ks, perm, run, n, wbits, uniq, n_uniq, pair_doc, pair_word, head, seq,
+                                             nnz);
+    ONI_TRY(window_pass(cub, cbytes, perm, iota, seq, wval, n, s));
+    k_scatter<<<nblk8(n), kB, 0, s>>>(iota, wval, n, tok_pair);
+  } else {
+    k_dp_scatter<false><<<nblk(n), kB, 0, s>>>(ks, perm, run, n, wbits, uniq, n_uniq, pair_doc, pair_word, head,
+                                              tok_pair, nnz);
+  }
+  if (weight) {
+    k_weights_sorted<<<nblk(n), kB, 0, s>>>(weight, perm, n, ws);
+    ONI_TRY(hipcub::DeviceScan::InclusiveSum(cub, cbytes, ws, psum, (int)n, s));
+  }
+  k_pair_counts<<<nblk(n), kB, 0, s>>>(head, weight ? psum : nullptr, nnz, n, pair_cnt);
+  if (sel) ONI_TRY(hipcub::DeviceSelect::If(cub, cbytes, perm, order0, nsel, (int)n, BelowN{(int32_t)n0}, s));
+  return (int)hipGetLastError();
+}
+
+ONI_API int oni_doc_pair_build(const void* keys_a, int64_t n_a, const void* keys_b, int key_bytes,
+                               const int32_t* word, const int32_t* weight, int64_t n, int64_t V, uint64_t* uniq,
+                               int64_t* n_uniq, int32_t* pair_doc, int32_t* pair_word, int32_t* pair_cnt,
+                               int32_t* tok_pair, int64_t* nnz, int32_t* order0, int64_t n0, void* tmp,
+                               size_t* tmp_bytes, hipStream_t s) {
+  if (n >= (int64_t)1 << 31 || n < 0 || n_a < 0 || n_a > n || V < 1 || n0 < 0 || n0 > n ||
+      (n_a < n && !keys_b) || (n_a > 0 && !keys_a))
+    return (int)hipErrorInvalidValue;
+  if (key_bytes == 4)
+    return doc_pair_build_impl<uint32_t>(static_cast<const uint32_t*>(keys_a), n_a,
+                                         static_cast<const uint32_t*>(keys_b), word, weight, n, V, uniq, n_uniq,
+                                         pair_doc, pair_word, pair_cnt, tok_pair, nnz, order0, n0, tmp, tmp_bytes, s);
+  if (key_bytes == 8)
+    return doc_pair_build_impl<uint64_t>(static_cast<const uint64_t*>(keys_a), n_a,
+                                         static_cast<const uint64_t*>(keys_b), word, weight, n, V, uniq, n_uniq,
+                                         pair_doc, pair_word, pair_cnt, tok_pair, nnz, order0, n0, tmp, tmp_bytes, s);
+  return (int)hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------------------------
 // doc_layout: CSR pointers + chunk counts. scalars[3] ← (T, n_chunks, n_long_docs).
 // Outputs: doc_pair_ptr[D+1], doc_tok_ptr[D+1], pair_tokoff[nnz], chunk_first[D+1], long_rows[D]
 ONI_API int oni_doc_layout(const int32_t* pair_doc, const int32_t* pair_cnt, int64_t nnz, int64_t D, int L,

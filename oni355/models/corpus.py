@@ -127,14 +127,20 @@ def build_corpus(tdoc: torch.Tensor, tword: torch.Tensor, D: int, V: int, doc_ke
     """Build pairs/CSR/SELL from token (doc id, word id[, weight]) arrays (any device).
 
     On a GPU the native kernels run (``pairs``: an already built :class:`oni355.ops.corpus.PairSet`
-    of exactly these tokens); ``native=False`` forces the torch reference build."""
-    dev = tdoc.device
-    if tdoc.numel() != tword.numel():
+    of exactly these tokens); ``native=False`` forces the torch reference build. ``tdoc`` may be
+    None with ``pairs`` (a fused doc-and-pair build has no token-order doc ids): the torch build
+    then reads each token's doc off its pair."""
+    dev = tword.device
+    if tdoc is None and pairs is None:
+        raise ValueError("build_corpus: token doc ids or their PairSet")
+    if tdoc is not None and tdoc.numel() != tword.numel():
         raise ValueError("tdoc/tword length mismatch")
     if L < 1 or L > (1 << 20):
         raise ValueError("chunk length L out of range")
     if dev.type == "cuda" and (NATIVE_DEVICE_BUILD if native is None else native):
         return _build_corpus_native(tdoc, tword, D, V, doc_keys, G, L, weight, pairs)
+    if tdoc is None:
+        tdoc = pairs.pair_doc[pairs.tok_pair.long()]
     S = 64 // G
     key = tdoc.to(torch.int64) * V + tword.to(torch.int64)
     if weight is None:

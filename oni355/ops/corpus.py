@@ -27,6 +27,7 @@ _lib.register("oni_partition", [vp, vp, vp, i64, ci, vp, vp, vp, vp, vp, _SZ, vp
 _lib.register("oni_place_stats", [vp, vp, i64, vp, i64, ci, vp, vp])
 _lib.register("oni_place_owner", [vp, i64, vp, i64, vp, ci, vp, vp, vp])
 _lib.register("oni_pair_build", [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, _SZ, vp])
+_lib.register("oni_doc_pair_build", [vp, i64, vp, ci, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, _SZ, vp])
 _lib.register("oni_doc_layout", [vp, vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, _SZ, vp])
 _lib.register("oni_chunk_layout", [vp, vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, _SZ, vp])
 _lib.register("oni_word_index", [vp, i64, i64, i64, ci, vp, vp, vp, vp, vp, vp, _SZ, vp])
@@ -283,6 +284,61 @@ def pair_build(doc: torch.Tensor, word: torch.Tensor, D: int, V: int, weight: to
           _p(pd), _p(pw), _p(pc), _p(tp), _p(nnz), _p(o0) if o0 is not None else None, int(n0))
     m = int(nnz.item())
     return PairSet(pd[:m], pw[:m], pc[:m], tp[:n], o0.to(torch.int64) if o0 is not None else None, int(D), int(V))
+
+
+def _doc_pair_build_torch(keys64: torch.Tensor, word: torch.Tensor, V: int, weight: torch.Tensor | None, n0: int):
+    """Torch reference of :func:`doc_pair_build` (CPU tensors): ``torch.unique`` + ``torch_pairs``."""
+    from ..pipeline.common import torch_pairs
+    n = keys64.numel()
+    udoc, inv = torch.unique(keys64, return_inverse=True)
+    tp = torch_pairs(inv.to(torch.int32), word, V)
+    w = weight.to(torch.int64) if weight is not None else torch.ones(n, dtype=torch.int64, device=keys64.device)
+    cnt = torch.zeros(tp.pair_doc.numel(), dtype=torch.int64, device=keys64.device).index_add_(0, tp.tok_pair.long(), w)
+    o0 = torch.argsort(tp.tok_pair[:n0], stable=True) if n0 > 0 else None
+    return udoc, PairSet(tp.pair_doc, tp.pair_word, cnt.clamp_(max=0x7FFFFFFF).to(torch.int32), tp.tok_pair, o0,
+                         int(udoc.numel()), int(V))
+
+
+def doc_pair_build(doc_keys, word: torch.Tensor, V: int, weight: torch.Tensor | None = None, n0: int = 0):
+    """``dict_encode(doc_keys, 32)`` + ``pair_build(ids, word, D, V, weight, n0)`` in one doc-and-pair
+    sort (``oni_doc_pair_build``): (sorted unique doc keys int64 [D], :class:`PairSet`), bit for bit
+    what the two calls return, without the token-order doc ids nobody reads at world 1.
+
+    ``doc_keys``: int64 keys below 2^32, int32 u32 bits, or a pair of int32 tensors whose
+    concatenation is the token list (a flow's source and destination addresses: no copy is made).
+    ``order0`` is built only for ``n0 > 0``. CPU tensors take the torch reference."""
+    parts = list(doc_keys) if isinstance(doc_keys, (tuple, list)) else [doc_keys]
+    if not 1 <= len(parts) <= 2 or any(p.dtype != parts[0].dtype or p.device != word.device for p in parts):
+        raise TypeError("doc_pair_build: doc keys are one tensor or two of one dtype, on the words' device")
+    if parts[0].dtype not in (torch.int32, torch.int64) or (len(parts) == 2 and parts[0].dtype != torch.int32):
+        raise TypeError("doc_pair_build: int64 keys, int32 u32 bits, or two int32 halves")
+    n = word.numel()
+    if word.dtype != torch.int32 or not word.is_contiguous() or sum(p.numel() for p in parts) != n:
+        raise TypeError(f"doc_pair_build: word must be contiguous int32, one per doc key [{n}]")
+    if weight is not None and (weight.dtype != torch.int32 or weight.numel() != n):
+        raise TypeError("doc_pair_build: weight must be int32 [n]")
+    if not 0 <= n0 <= n:
+        raise ValueError("doc_pair_build: n0 out of range")
+    if V < 1:
+        raise ValueError("doc_pair_build: V >= 1")
+    dev = word.device
+    if dev.type != "cuda":
+        k = torch.cat(parts) if len(parts) == 2 else parts[0]
+        return _doc_pair_build_torch(k.to(torch.int64) & 0xFFFFFFFF, word, V, weight, n0)
+    parts = [p.contiguous() for p in parts]
+    uniq = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    nu = torch.zeros(2, dtype=torch.int64, device=dev)  # (D, nnz): one host read for both
+    pd = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    pw = torch.empty_like(pd)
+    pc = torch.empty_like(pd)
+    tp = torch.empty_like(pd)
+    o0 = torch.empty(n0, dtype=torch.int32, device=dev) if n0 > 0 else None
+    _call("oni_doc_pair_build", _p(parts[0]) if parts[0].numel() else None, parts[0].numel(),
+          _p(parts[1]) if len(parts) == 2 and parts[1].numel() else None, parts[0].element_size(), _p(word) if n else None,
+          _p(weight.contiguous()) if weight is not None else None, n, int(V), _p(uniq), _lib.ptr(nu), _p(pd), _p(pw),
+          _p(pc), _p(tp), _lib.ptr(nu) + 8, _p(o0) if o0 is not None else None, int(n0))
+    D, m = (int(x) for x in nu.tolist())
+    return uniq[:D], PairSet(pd[:m], pw[:m], pc[:m], tp[:n], o0.to(torch.int64) if o0 is not None else None, D, int(V))
 
 
 def corpus_layout(ps: PairSet, doc_keys: torch.Tensor, G: int, L: int, recount_tile: int):

@@ -120,6 +120,20 @@ def encode_docs(doc_keys64: torch.Tensor, key_bits: int = 32):
     return u, inv.to(torch.int32)
 
 
+def fused_corpus(dev, comm: Comm | None) -> bool:
+    """Does :func:`build_and_train` build the doc dictionary and the pairs in one sort? One rank on
+    a GPU (doc keys are u32 bits everywhere, see :func:`encode_docs`); such a caller may hand its
+    doc keys over as int32 u32 bits, or as the two int32 halves of the token list."""
+    return torch.device(dev).type == "cuda" and (comm is None or not comm.dist)
+
+
+@traced("oni:doc_pair_build")
+def encode_docs_pairs(doc_keys, word_ids: torch.Tensor, V: int, weights: torch.Tensor | None, n0: int):
+    """(sorted unique doc keys int64, PairSet of the tokens): :func:`encode_docs` + the pair build."""
+    from ..ops import corpus as oc
+    return oc.doc_pair_build(doc_keys, word_ids, V, weights, n0=n0)
+
+
 def doc_owner(doc_keys64: torch.Tensor, world: int) -> torch.Tensor:
     """Owner rank of each document: multiplicative hash of the u32 key (spreads /24 subnets)."""
     h = (doc_keys64 * 0x9E3779B1) & U32MASK
@@ -536,6 +550,8 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
     """Token keys → owner routing → local corpus → Gibbs LDA trained for ``sweeps`` sweeps.
 
     ``word_ids`` (int32, from :func:`encode_words`) skips the vocabulary lookup of ``word_keys64``.
+    Where :func:`fused_corpus` holds, ``doc_keys64`` may also be int32 u32 bits or the two int32
+    halves of the token list (``ops.corpus.doc_pair_build``).
     ``n_event0``: the first ``n_event0`` tokens are the events' first endpoints (world 1: the
     corpus pair build then also yields the score plan's event order, see :func:`plan_from_pairs`).
     ``ldac_dir`` + ``ldac_lag`` > 0 emit lda-c ``NNN.{beta,gamma,other}`` snapshots every
@@ -546,7 +562,8 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
     ``on_train()`` is called as the sweeps start (e.g. to queue the next day's upload on a copy
     stream: training needs no host↔device transfers, while the collectives of the earlier stages
     would wait behind a bulk copy on the DMA engine)."""
-    dev = doc_keys64.device
+    key_parts = doc_keys64 if isinstance(doc_keys64, (tuple, list)) else (doc_keys64,)
+    dev = key_parts[0].device
     timer = timer or StageTimer(dev)
     dist_on = comm is not None and comm.dist
     with timer.stage("corpus"):
@@ -562,7 +579,7 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
         if chunk_len <= 0:
             # the global (weighted) token count picks L -- before routing: the placement cuts
             # heavy documents at multiples of L
-            T_glob = float(weights.sum()) if use_w else float(doc_keys64.numel())
+            T_glob = float(weights.sum()) if use_w else float(sum(p.numel() for p in key_parts))
             if dist_on:
                 T_glob = comm.allreduce_scalar(T_glob, "sum")
             # the MH sampler's u8 LDS cells hold a chunk's count deltas: chunks ≤ 127 tokens
@@ -574,17 +591,26 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                 log(f"chunk_len {chunk_len} -> {spec.MH_MAX_CHUNK}: the MH sampler's chunks hold at most "
                     f"{spec.MH_MAX_CHUNK} tokens")
             chunk_len = spec.MH_MAX_CHUNK
-        udoc, inv, wi, wt, route = route_to_owners(doc_keys64, word_ids, weights, comm,
-                                                   split_L=chunk_len if dist_on else 0)
-        D, V = int(udoc.numel()), int(vocab.numel())
-        pairs = None
-        if dev.type == "cuda":
-            from ..ops import corpus as oc
-            pairs = oc.pair_build(inv, wi.to(torch.int32).contiguous(), D, V,
-                                  wt.to(torch.int32).contiguous() if use_w else None,
-                                  n0=0 if dist_on else int(n_event0))
-        elif dist_on:
-            pairs = torch_pairs(inv, wi, V)
+        V = int(vocab.numel())
+        if fused_corpus(dev, comm):
+            # one rank: nothing reads the token-order doc ids but the pair build, so the doc
+            # dictionary and the pairs come out of one sort (ops.corpus.doc_pair_build); the
+            # pair-ordered event view is built only where plan_from_pairs reads it
+            wi, wt, inv, route = word_ids.to(torch.int32).contiguous(), weights, None, None
+            udoc, pairs = encode_docs_pairs(doc_keys64, wi, V, wt.to(torch.int32).contiguous() if use_w else None,
+                                            int(n_event0) if SCORE_SORT_PAIRS else 0)
+            D = pairs.D
+        else:
+            udoc, inv, wi, wt, route = route_to_owners(doc_keys64, word_ids, weights, comm,
+                                                       split_L=chunk_len if dist_on else 0)
+            D = int(udoc.numel())
+            pairs = None
+            if dev.type == "cuda":
+                from ..ops import corpus as oc
+                pairs = oc.pair_build(inv, wi.to(torch.int32).contiguous(), D, V,
+                                      wt.to(torch.int32).contiguous() if use_w else None, n0=0)
+            elif dist_on:
+                pairs = torch_pairs(inv, wi, V)
         plan = route.split if route is not None else None
         if plan is not None:
             # heavy documents cut across ranks: the corpus holds this rank's pieces (pairs clipped

@@ -245,10 +245,13 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
         sw, dw = wordify(d, cuts)
     with timer.stage("vocab"):
         n = d["sip"].numel()
-        doc_keys = ops.widen_pair(d["sip"], d["dip"])
         word_keys = ops.widen_pair(sw, dw)
         weights = None
         fb = feedback_tokens(feedback, cuts, device, dupfactor)
+        # one rank on a GPU, no feedback tokens to append: the fused doc-and-pair build reads the
+        # two address columns as they are (u32 bits), no widened [sip ‖ dip] copy
+        halves = fb is None and common.fused_corpus(d["sip"].device, comm)
+        doc_keys = (d["sip"], d["dip"]) if halves else ops.widen_pair(d["sip"], d["dip"])
         if fb is not None:
             # every rank reads the same feedback file: all of them carry token weights (the
             # routing exchanges the same columns everywhere), only rank 0 adds the tokens
@@ -280,6 +283,8 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
             if run.pairs is not None and not common.SCORE_TILES:
                 plan = common.plan_from_pairs(run.pairs, n, 2)  # the corpus pair build holds the plan
             else:
+                if halves:
+                    doc_keys = ops.widen_pair(d["sip"], d["dip"])
                 plan = common.event_score_plan(run, dkeys, vocab, [doc_keys[:n], doc_keys[n: 2 * n]], wids[: 2 * n],
                                                [word_keys[:n], word_keys[n: 2 * n]], comm)
         with timer.stage("score"):
