@@ -5,11 +5,14 @@
   infer    score_flow against a model trained once (every sweep of a single-chunk document in one
            launch)
   unfused  score_flow with sweep fusion off (one launch per sweep)
+  prior    score_flow, fused, with the model's per-IP topic profiles as priors (--prior-mass)
 
   python bench/foldin.py --flows 12500000 --topics 20 --rounds 3 --out profiles/foldin/bench.json
 
 Prints one JSON line per day and a summary: median / min ms per day, ms per fold-in sweep (the
 ``foldin`` stage over the fold-in sweeps) and the run-to-run spread (max − min) of every variant.
+The model is saved with its document profiles; ``model_bytes`` is the size of that file with and
+without them. ``--variants`` picks the variants that alternate (default: all four).
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import json
 import os
 import statistics
 import sys
+import tempfile
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,6 +36,8 @@ def main() -> int:
     ap.add_argument("--avg-last", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--prior-mass", type=float, default=5.0, help="the prior variant's mass")
+    ap.add_argument("--variants", default="train,infer,unfused,prior")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
@@ -53,13 +59,21 @@ def main() -> int:
     # the model is trained once (this untimed day is also the warm-up of the training variant)
     first = run_flow(day.cols, K=a.topics, sweeps=a.sweeps, **kw)
     model = SavedModel.from_run(first.lda, first.cuts, "flow", {"day": "bench"})
+    with tempfile.TemporaryDirectory() as td:
+        model_bytes = {"with_docs": os.path.getsize(model.save(os.path.join(td, "m.npz"))),
+                       "without_docs": os.path.getsize(model.without_docs().save(os.path.join(td, "m0.npz")))}
+    print(json.dumps({"model_bytes": model_bytes, "model_docs": int(model.doc_keys.shape[0]), "V": model.V}), flush=True)
     top_train = set(first.rows.tolist())
     del first
     ikw = dict(sweeps=a.infer_sweeps, avg_last=a.avg_last, **kw)
-    score_flow(day.cols, model, **ikw)  # untimed warm-up of the fold-in variants
     variants = {"train": lambda: run_flow(day.cols, K=a.topics, sweeps=a.sweeps, **kw),
                 "infer": lambda: score_flow(day.cols, model, **ikw),
-                "unfused": lambda: score_flow(day.cols, model, fuse=False, **ikw)}
+                "unfused": lambda: score_flow(day.cols, model, fuse=False, **ikw),
+                "prior": lambda: score_flow(day.cols, model, prior_mass=a.prior_mass, **ikw)}
+    variants = {n: variants[n] for n in a.variants.split(",")}
+    for n, fn in variants.items():  # untimed warm-up of the fold-in variants
+        if n != "train":
+            fn()
     days = {n: [] for n in variants}
     for r in range(a.rounds):
         for name, fn in variants.items():
@@ -75,6 +89,8 @@ def main() -> int:
             else:
                 line["ms_per_sweep"] = round(t.get("foldin_dev_s", t.get("foldin_s", 0.0)) / max(a.infer_sweeps, 1) * 1e3, 4)
                 line["launches"] = res.stats["foldin_launches"]
+                if name == "prior":
+                    line["n_prior_docs"] = res.stats["n_prior_docs"]
                 line["overlap_with_training"] = round(len(top_train & set(res.rows.tolist())) / max(len(top_train), 1), 4)
             days[name].append(line)
             print(json.dumps(line), flush=True)
@@ -87,7 +103,8 @@ def main() -> int:
                 "ms_per_sweep_spread": round(max(s) - min(s), 4)}
     summary = {n: summ(v) for n, v in days.items()}
     out = {"flows": a.flows, "topics": a.topics, "train_sweeps": a.sweeps, "infer_sweeps": a.infer_sweeps,
-           "avg_last": a.avg_last, "rounds": a.rounds, "summary": summary, "days": days}
+           "avg_last": a.avg_last, "rounds": a.rounds, "prior_mass": a.prior_mass, "model_bytes": model_bytes,
+           "summary": summary, "days": days}
     print(json.dumps({"summary": summary}), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

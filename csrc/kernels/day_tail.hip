@@ -116,6 +116,40 @@ __global__ __launch_bounds__(256) void k_theta_rows(const C* __restrict__ n, int
   }
 }
 
+// θ under per-document prior rows (fold-in with priors): as k_theta_rows, with the flat additions
+// replaced by the document's own row. num_j = fma(S, pr_j, f32(n_j)); den = fma(S, Σ_j pr_j, f32(n_d)),
+// the prior sum taken in f32 in column order (oni355/ref/foldin_spec.py theta_rows_prior).
+template <typename C>
+__global__ __launch_bounds__(256) void k_theta_rows_prior(const C* __restrict__ n, const float* __restrict__ pr,
+                                                          int64_t D, int K, int KS, float S, float* __restrict__ th) {
+  __shared__ float den[256];
+  for (int64_t r0 = (int64_t)blockIdx.x * 256; r0 < D; r0 += (int64_t)gridDim.x * 256) {
+    const int64_t d = r0 + threadIdx.x;
+    if (d < D) {
+      const C* r = n + d * KS;
+      const float* p = pr + d * KS;
+      int64_t nd = 0;
+      float sp = 0.f;
+      for (int k = 0; k < K; ++k) {
+        nd += r[k];
+        sp = sp + p[k];
+      }
+      den[threadIdx.x] = fmaf(S, sp, (float)nd);
+    }
+    __syncthreads();
+    const int64_t rows = D - r0 < 256 ? D - r0 : 256;
+    const int64_t cells = rows * KS;
+    const C* src = n + r0 * KS;
+    const float* psrc = pr + r0 * KS;
+    float* dst = th + r0 * KS;
+    for (int64_t i = threadIdx.x; i < cells; i += 256) {
+      const int k = (int)(i % KS);
+      dst[i] = k < K ? fmaf(S, psrc[i], (float)src[i]) / den[i / KS] : 0.f;
+    }
+    __syncthreads();
+  }
+}
+
 template <typename C, typename CK>
 __global__ __launch_bounds__(256) void k_phi_rows(const C* __restrict__ nw, const CK* __restrict__ nk,
                                                   int64_t V, int K, int KS, float add, float vb,
@@ -156,6 +190,19 @@ ONI_API int oni_theta_rows(const void* n, int64_t D, int K, int KS, float add, f
     k_theta_rows<int64_t><<<grid, 256, 0, s>>>(static_cast<const int64_t*>(n), D, K, KS, add, den_add, th);
   else
     k_theta_rows<int32_t><<<grid, 256, 0, s>>>(static_cast<const int32_t*>(n), D, K, KS, add, den_add, th);
+  return (int)hipGetLastError();
+}
+
+// pr: f32 [D][KS] prior rows; S: window samples; csize as above
+ONI_API int oni_theta_rows_prior(const void* n, const float* pr, int64_t D, int K, int KS, float S, float* th,
+                                 int csize, hipStream_t s) {
+  if (K < 1 || K > KS || (csize != 4 && csize != 8)) return (int)hipErrorInvalidValue;
+  if (D <= 0) return 0;
+  const unsigned grid = oni::grid_for(D, 256, 2048);
+  if (csize == 8)
+    k_theta_rows_prior<int64_t><<<grid, 256, 0, s>>>(static_cast<const int64_t*>(n), pr, D, K, KS, S, th);
+  else
+    k_theta_rows_prior<int32_t><<<grid, 256, 0, s>>>(static_cast<const int32_t*>(n), pr, D, K, KS, S, th);
   return (int)hipGetLastError();
 }
 

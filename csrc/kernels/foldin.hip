@@ -22,6 +22,11 @@
 // over several chunks need their chunks' Δ merged between sweeps: they are swept one sweep per
 // launch (`select` 2, sweep-start row in ndk_src, Δ added into the pre-copied row of ndk_dst), and
 // the host adds their window sums.
+//
+// Per-document priors (`prior`, the PRIOR instantiations): a document the saved model has a profile
+// of draws from (n_dk^¬t + pr_dk)·φ_wk with pr_dk = α + m_d·θ^train_dk. A live unit loads its KP
+// columns of the row once, before the sweeps, and forms a_j = f32(n_j) + pr_j at use; the rows are
+// made by k_prior_rows below (oni355/ref/foldin_spec.py prior_rows).
 #include "gibbs_sampler.h"
 
 struct OniFoldin {
@@ -46,11 +51,12 @@ struct OniFoldin {
   int32_t n_sweeps;            // sweeps run back to back (> 1: single-chunk chunks only)
   int32_t avg_from;            // first sweep whose rows enter ndk_sum
   int32_t select;              // 0 every chunk, 1 chunks of single-chunk docs, 2 chunks of multi-chunk docs
+  const float* prior;          // [D][KS] per-document prior rows in α's place; nullptr = the flat prior α
 };
 
 namespace {
 
-template <int G, int KP, bool INIT>
+template <int G, int KP, bool INIT, bool PRIOR>
 __global__ __launch_bounds__(kBlock) void k_foldin(const OniFoldin a) {
   constexpr int S = oni::kWave / G;
   constexpr int KS = G * KP;
@@ -86,6 +92,14 @@ __global__ __launch_bounds__(kBlock) void k_foldin(const OniFoldin a) {
 #pragma unroll
   for (int j = 0; j < KP; ++j) qv[j] = 0.f;
   uint32_t wprev = oni::kPadWord;
+  // the document's prior row (the same row in every chunk of a multi-chunk document); a dead unit
+  // reads none and draws nothing
+  float pr[PRIOR ? KP : 1];
+  if constexpr (PRIOR) {
+#pragma unroll
+    for (int j = 0; j < KP; ++j) pr[j] = 0.f;
+    if (live) load_row_f<KP>(a.prior + (int64_t)doc * KS + kbase, pr);
+  }
 
   const int n_sweeps = INIT ? 1 : a.n_sweeps;
   for (int it = 0; it < n_sweeps; ++it) {
@@ -117,7 +131,10 @@ __global__ __launch_bounds__(kBlock) void k_foldin(const OniFoldin a) {
       float run = 0.f;
 #pragma unroll
       for (int j = 0; j < KP; ++j) {
-        run = fmaf((float)n[j] + a.alpha, qv[j], run);
+        float add;
+        if constexpr (PRIOR) add = pr[j];
+        else add = a.alpha;
+        run = fmaf((float)n[j] + add, qv[j], run);
         P[j] = run;
       }
       float excl = 0.f, total = run;
@@ -185,12 +202,58 @@ int launch_foldin(const OniFoldin& a, bool init, hipStream_t s) {
   if (a.KS != G * KP) return (int)hipErrorInvalidValue;
   const unsigned grid = (unsigned)((a.n_slices + kWavesPerBlock - 1) / kWavesPerBlock);
   if (grid == 0) return 0;
-  if (init) k_foldin<G, KP, true><<<grid, kBlock, 0, s>>>(a);
-  else k_foldin<G, KP, false><<<grid, kBlock, 0, s>>>(a);
+  if (a.prior != nullptr) {
+    if (init) k_foldin<G, KP, true, true><<<grid, kBlock, 0, s>>>(a);
+    else k_foldin<G, KP, false, true><<<grid, kBlock, 0, s>>>(a);
+  } else {
+    if (init) k_foldin<G, KP, true, false><<<grid, kBlock, 0, s>>>(a);
+    else k_foldin<G, KP, false, false><<<grid, kBlock, 0, s>>>(a);
+  }
   return (int)hipGetLastError();
 }
 
+// One thread per batch document: binary search of its key in the model's sorted keys, then its KS
+// columns. m = min(f32(tokens), mass); pr_j = fma(m, θ_j, α) for j < K of a known document below
+// the per-day IPv6 ids, α everywhere else.
+constexpr int64_t kV6KeyBase = 0xF0000000ll;
+
+__global__ __launch_bounds__(256) void k_prior_rows(const int64_t* __restrict__ mkeys, const float* __restrict__ mtheta,
+                                                    const int64_t* __restrict__ mtokens, int64_t Dm,
+                                                    const int64_t* __restrict__ keys, int64_t D, int K, int KS,
+                                                    float alpha, float mass, float* __restrict__ out) {
+  for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < D; d += (int64_t)gridDim.x * 256) {
+    const int64_t key = keys[d];
+    int64_t lo = 0, hi = Dm;  // first model key ≥ key
+    while (lo < hi) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      if (mkeys[mid] < key) lo = mid + 1;
+      else hi = mid;
+    }
+    const bool hit = lo < Dm && mkeys[lo] == key && key < kV6KeyBase;
+    float* o = out + d * KS;
+    if (hit) {
+      const float tk = (float)mtokens[lo];
+      const float m = tk < mass ? tk : mass;
+      const float* th = mtheta + lo * K;
+      for (int j = 0; j < K; ++j) o[j] = fmaf(m, th[j], alpha);
+      for (int j = K; j < KS; ++j) o[j] = alpha;
+    } else {
+      for (int j = 0; j < KS; ++j) o[j] = alpha;
+    }
+  }
+}
+
 }  // namespace
+
+// mkeys int64 [Dm] strictly ascending, mtheta f32 [Dm][K], mtokens int64 [Dm]; keys int64 [D]; out f32 [D][KS]
+ONI_API int oni_prior_rows(const int64_t* mkeys, const float* mtheta, const int64_t* mtokens, int64_t Dm,
+                           const int64_t* keys, int64_t D, int K, int KS, float alpha, float mass, float* out,
+                           hipStream_t s) {
+  if (K < 1 || K > KS || Dm < 0 || D < 0) return (int)hipErrorInvalidValue;
+  if (D == 0) return 0;
+  k_prior_rows<<<oni::grid_for(D, 256, 2048), 256, 0, s>>>(mkeys, mtheta, mtokens, Dm, keys, D, K, KS, alpha, mass, out);
+  return (int)hipGetLastError();
+}
 
 ONI_API int oni_foldin_sizeof_args() { return (int)sizeof(OniFoldin); }
 

@@ -54,10 +54,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--ldac-lag", type=int, default=0, help="also write lda-c NNN.* snapshots every N sweeps")
     ap.add_argument("--save-model", metavar="DIR", default=None,
                     help="after training, write DIR/<source>_model.npz (the model --model scores against)")
+    ap.add_argument("--no-model-docs", action="store_true",
+                    help="--save-model: leave the day's per-IP topic profiles out of the model file")
     ap.add_argument("--model", metavar="FILE", default=None,
                     help="score the day's events against this saved model (fold-in inference) instead of training")
     ap.add_argument("--infer-sweeps", type=int, default=30, help="--model: fold-in sweeps")
     ap.add_argument("--infer-avg-last", type=int, default=10, help="--model: sweeps averaged into theta")
+    ap.add_argument("--infer-prior-mass", type=float, default=0.0, metavar="M",
+                    help="--model: fold an IP the model knows in under its training-day topic profile, weighted "
+                         "by at most M pseudo-tokens (0: off, every IP starts from the flat prior)")
     ap.add_argument("--burnin", type=int, default=None, help="sweeps before the likelihood trace / snapshots")
     ap.add_argument("--max-restarts", type=int, default=0,
                     help="supervise the run: after a failure (crash, watchdog exit, numerical fault) start a "
@@ -254,6 +259,8 @@ def main(argv=None) -> int:
                 raise SystemExit(f"oni-ml: --model scores against a saved model and trains nothing; {flag} does not apply")
         if not os.path.isfile(a.model):
             raise SystemExit(f"oni-ml: --model {a.model}: no such file")
+        if a.infer_prior_mass < 0:
+            raise SystemExit("oni-ml: --infer-prior-mass must be ≥ 0")
     if a.max_restarts > 0 and os.environ.get("ONI_SUPERVISED") != "1":
         if inside:
             # the supervisor's children would write to the service's stdout, not the client's
@@ -315,16 +322,20 @@ def main(argv=None) -> int:
         from ..pipeline.flow import score_flow
         model = SavedModel.load(a.model)
         log(f"model {a.model}: K={model.K}, V={model.V}, trained {model.provenance}")
+        if a.infer_prior_mass > 0 and not model.has_docs:
+            raise SystemExit(f"oni-ml: --infer-prior-mass needs per-IP topic profiles, which {a.model} was saved "
+                             "without: save the model again with --save-model and no --no-model-docs")
         res = score_flow(cols, model, tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps,
                          avg_last=a.infer_avg_last, seed=cfg.SEED, device=device, comm=comm, feedback=fb,
-                         chunk_len=cfg.CHUNK_LEN, row_offset=row_off, log=log)
+                         chunk_len=cfg.CHUNK_LEN, row_offset=row_off, log=log,
+                         prior_mass=a.infer_prior_mass)
     elif a.source == "flow":
         from ..pipeline.flow import run_flow
         res = run_flow(cols, **common_kw)
         if a.save_model:
             from ..models.saved import SavedModel
             os.makedirs(a.save_model, exist_ok=True)
-            mp = SavedModel.from_run(res.lda, res.cuts, "flow", {"day": a.date}).save(
+            mp = SavedModel.from_run(res.lda, res.cuts, "flow", {"day": a.date}, docs=not a.no_model_docs).save(
                 os.path.join(a.save_model, "flow_model.npz"))
             log(f"saved model -> {mp}")
     elif a.source == "dns":

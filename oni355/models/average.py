@@ -24,6 +24,15 @@ def theta_rows(ndk: torch.Tensor, K: int, add: float, den_add: float) -> torch.T
     return th.contiguous()
 
 
+def theta_rows_prior(ndk_sum: torch.Tensor, prior: torch.Tensor, K: int, S: float) -> torch.Tensor:
+    """θ[d,k] = (Σn_dk + S·pr_dk)/(Σn_d + S·Σ_k pr_dk) of documents folded in under per-document prior
+    rows ``prior`` (f32 [D, KS]) over S window samples, the padding columns zero. Numerator and
+    denominator are single f32 fmas (k_theta_rows_prior on a GPU); torch has no fma whose rounding
+    is pinned on the CPU, so CPU tensors take the NumPy expression of
+    :func:`oni355.ref.foldin_spec.theta_rows_prior`: CPU and GPU θ agree bit for bit."""
+    return ops.theta_rows_prior(ndk_sum, prior, K, S)
+
+
 class PosteriorAverage:
     """The averaging schedule (``at``: the sweep counts at which a sample is added), the sample
     sums ``wk``, ``k``, ``dk`` of n_wk, n_k, n_dk (allocated at the first sample), the number

@@ -15,17 +15,19 @@ import torch
 from .. import ops
 from ..ref import foldin_spec
 from ..utils.obs import traced
-from .average import theta_rows
+from .average import theta_rows, theta_rows_prior
 from .corpus import Corpus
 
 
 class FoldIn:
     """Device (or CPU-oracle) state of one fold-in run over ``corpus`` (word ids index ``table``:
     f32 [V + 1, KS] from :meth:`oni355.models.saved.SavedModel.table`, row V = unseen words).
-    ``fuse=False`` launches every sweep on its own (the A/B of bench/foldin.py; same draws)."""
+    ``fuse=False`` launches every sweep on its own (the A/B of bench/foldin.py; same draws).
+    ``prior``: f32 [D, KS] per-document Dirichlet rows (ops.prior_rows) that take α's place on the
+    doc side of the draws and of θ; None is the flat prior α."""
 
     def __init__(self, corpus: Corpus, table: torch.Tensor, K: int, alpha: float, seed: int = 0x0D15EA5E,
-                 fuse: bool = True):
+                 fuse: bool = True, prior: torch.Tensor | None = None):
         c = corpus
         if table.dim() != 2 or table.dtype != torch.float32 or table.shape[0] != c.V:
             raise ValueError(f"the word table must be f32 [{c.V}, KS] (one row per corpus word id)")
@@ -40,6 +42,11 @@ class FoldIn:
         self.G, self.KS = c.G, int(table.shape[1])
         self.KP = self.KS // self.G
         dev = self.device = c.tok_word.device
+        if prior is not None:
+            if prior.dtype != torch.float32 or tuple(prior.shape) != (max(c.D, 1), self.KS) or prior.device != dev:
+                raise ValueError(f"the prior must be f32 [{max(c.D, 1)}, {self.KS}] on the corpus' device")
+            prior = prior.contiguous()
+        self.prior = prior
         self.tok_z = torch.zeros(c.sell_slots, dtype=torch.uint8, device=dev)
         self.ndk = torch.zeros(max(c.D, 1), self.KS, dtype=torch.int32, device=dev)
         self.ndk_sum = torch.zeros_like(self.ndk)
@@ -50,7 +57,10 @@ class FoldIn:
         self.launches = {"init": 0, "sweep": 0, "multi_sweep": 0}
 
     def _state(self, src: torch.Tensor, dst: torch.Tensor) -> dict:
-        return dict(self.c.sell_state(self.tok_z), ndk_src=src, ndk_dst=dst, ndk_sum=self.ndk_sum, phi=self.table)
+        st = dict(self.c.sell_state(self.tok_z), ndk_src=src, ndk_dst=dst, ndk_sum=self.ndk_sum, phi=self.table)
+        if self.prior is not None:
+            st["prior"] = self.prior
+        return st
 
     def _pass(self, st: dict, init: bool, sweep_lo: int, n_sweeps: int, avg_from: int, select: int) -> None:
         ops.foldin_pass(st, self.G, self.KP, self.K, self.alpha, self.seed, init, sweep_lo, n_sweeps, avg_from,
@@ -98,8 +108,11 @@ class FoldIn:
         return self
 
     def theta(self) -> torch.Tensor:
-        """θ = (Σn_dk + S·α)/(Σn_d + S·K·α) over the S window samples, KS-padded with zeros."""
+        """θ = (Σn_dk + S·α)/(Σn_d + S·K·α) over the S window samples, KS-padded with zeros; with a
+        prior, (Σn_dk + S·pr_dk)/(Σn_d + S·Σ_k pr_dk)."""
         S, K = float(max(self.samples, 1)), self.K
+        if self.prior is not None:
+            return theta_rows_prior(self.ndk_sum, self.prior, K, S)
         return theta_rows(self.ndk_sum, K, S * self.alpha, S * K * self.alpha)
 
     def phi(self) -> torch.Tensor:

@@ -3,17 +3,23 @@
 One ``.npz`` (no pickle) holding the word table φ of a finished training run, the vocabulary it is
 indexed by, the row of a never-seen word, the feature cuts the words were made with and a small
 provenance record. lda-c's ``final.beta`` + ``final.other`` play this role for the VEM engine.
+Optionally it also keeps the training day's document profiles (``doc_keys``, ``doc_theta``,
+``doc_tokens``; lda-c's ``final.gamma``), which fold-in can use as per-IP topic priors.
 """
 from __future__ import annotations
 
 import json
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 import torch
 
+from ..ref.foldin_spec import V6_KEY_BASE  # keys from here up are per-day IPv6 ids: never saved
+
 FORMAT = 1
 _ARRAYS = ("vocab", "phi", "phi_oov", "cuts_time", "cuts_ibyt", "cuts_ipkt")
+# the optional document profiles: all three or none. An older build's loader ignores them.
+_DOC_ARRAYS = ("doc_keys", "doc_theta", "doc_tokens")
 
 
 def oov_row(model) -> np.ndarray:
@@ -44,10 +50,22 @@ class SavedModel:
     phi_oov: np.ndarray    # f32 [K] row of a word the model never saw
     cuts: dict             # feature cuts as raw key arrays (flow: time / ibyt / ipkt, uint32)
     provenance: dict = field(default_factory=dict)
+    # the training day's document profiles (all three or none)
+    doc_keys: np.ndarray | None = None     # int64 [Dm] strictly ascending document (IP) keys
+    doc_theta: np.ndarray | None = None    # f32 [Dm, K] θ of each document at the end of training
+    doc_tokens: np.ndarray | None = None   # int64 [Dm] training tokens of each document
 
     @property
     def V(self) -> int:
         return int(self.vocab.shape[0])
+
+    @property
+    def has_docs(self) -> bool:
+        return self.doc_keys is not None
+
+    def without_docs(self) -> "SavedModel":
+        """The same model without its document profiles."""
+        return replace(self, doc_keys=None, doc_theta=None, doc_tokens=None)
 
     def __post_init__(self):
         self.vocab = np.ascontiguousarray(self.vocab, dtype=np.int64)
@@ -58,11 +76,25 @@ class SavedModel:
             raise ValueError(f"phi must be [V={self.V}, K={self.K}] and phi_oov [K]")
         if self.V > 1 and not bool((self.vocab[1:] > self.vocab[:-1]).all()):
             raise ValueError("vocab must be strictly ascending word keys")
+        given = [getattr(self, k) is not None for k in _DOC_ARRAYS]
+        if any(given) and not all(given):
+            raise ValueError("doc_keys, doc_theta and doc_tokens come together or not at all")
+        if all(given):
+            self.doc_keys = np.ascontiguousarray(self.doc_keys, dtype=np.int64)
+            self.doc_theta = np.ascontiguousarray(self.doc_theta, dtype=np.float32)
+            self.doc_tokens = np.ascontiguousarray(self.doc_tokens, dtype=np.int64)
+            Dm = self.doc_keys.shape[0] if self.doc_keys.ndim == 1 else -1
+            if Dm < 0 or self.doc_theta.shape != (Dm, self.K) or self.doc_tokens.shape != (Dm,):
+                raise ValueError(f"doc_keys must be [Dm], doc_theta [Dm, K={self.K}] and doc_tokens [Dm]")
+            if Dm > 1 and not bool((self.doc_keys[1:] > self.doc_keys[:-1]).all()):
+                raise ValueError("doc_keys must be strictly ascending document keys")
 
     @classmethod
-    def from_run(cls, run, cuts, source: str, cfg: dict | None = None) -> "SavedModel":
+    def from_run(cls, run, cuts, source: str, cfg: dict | None = None, docs: bool = True) -> "SavedModel":
         """The model of a finished training run (``run``: pipeline.common.LdaRun; ``cuts``: the
-        day's FlowCuts; ``cfg``: provenance such as the training day)."""
+        day's FlowCuts; ``cfg``: provenance such as the training day). ``docs``: keep the day's
+        document profiles (θ as scoring read it, and each document's token count), without the
+        documents keyed by the day's IPv6 dictionary."""
         from ..utils import provenance as prov
         m = run.model
         if run.route is not None or run.extra_models:
@@ -71,18 +103,27 @@ class SavedModel:
         prv = {"sweeps": int(m.sweeps_done), "seed": int(m.cfg.seed), "tree_hash": prov.tree_hash("hip"),
                "averaged": m._averaged() is not None}
         prv.update(cfg or {})
+        prof = {}
+        if docs:
+            from ..pipeline import common
+            dkeys, theta = common.gather_theta(run, None)
+            dkeys = dkeys.cpu().numpy().astype(np.int64)
+            keep = dkeys < V6_KEY_BASE
+            prof = {"doc_keys": dkeys[keep], "doc_theta": theta[:, :K].cpu().numpy()[keep],
+                    "doc_tokens": run.corpus.doc_lengths()[: dkeys.shape[0]].cpu().numpy().astype(np.int64)[keep]}
         return cls(source=source, K=K, alpha=float(m.alpha), beta=float(m.beta),
                    vocab=run.vocab.cpu().numpy(), phi=m.phi()[:, :K].cpu().numpy(), phi_oov=oov_row(m),
-                   cuts={"time": cuts.time, "ibyt": cuts.ibyt, "ipkt": cuts.ipkt}, provenance=prv)
+                   cuts={"time": cuts.time, "ibyt": cuts.ibyt, "ipkt": cuts.ipkt}, provenance=prv, **prof)
 
     def save(self, path: str) -> str:
         meta = {"format": FORMAT, "source": self.source, "K": int(self.K), "alpha": float(self.alpha),
                 "beta": float(self.beta), "provenance": self.provenance}
         if not path.endswith(".npz"):
             path += ".npz"
+        docs = {k: getattr(self, k) for k in _DOC_ARRAYS} if self.has_docs else {}
         with open(path, "wb") as f:
             np.savez(f, meta=np.array([json.dumps(meta, sort_keys=True)]), vocab=self.vocab, phi=self.phi,
-                     phi_oov=self.phi_oov, **{f"cuts_{k}": v for k, v in self.cuts.items()})
+                     phi_oov=self.phi_oov, **{f"cuts_{k}": v for k, v in self.cuts.items()}, **docs)
         return path
 
     @classmethod
@@ -95,9 +136,10 @@ class SavedModel:
             if meta.get("format") != FORMAT:
                 raise ValueError(f"{path}: model format {meta.get('format')} (this build reads {FORMAT})")
             arr = {k: z[k] for k in _ARRAYS}
+            docs = {k: z[k] for k in _DOC_ARRAYS if k in z.files}
         return cls(source=meta["source"], K=int(meta["K"]), alpha=float(meta["alpha"]), beta=float(meta["beta"]),
                    vocab=arr["vocab"], phi=arr["phi"], phi_oov=arr["phi_oov"],
-                   cuts={k[5:]: arr[k] for k in _ARRAYS if k.startswith("cuts_")}, provenance=meta.get("provenance", {}))
+                   cuts={k[5:]: arr[k] for k in _ARRAYS if k.startswith("cuts_")}, provenance=meta.get("provenance", {}), **docs)
 
     def table(self, G: int, KP: int, device) -> torch.Tensor:
         """The sampler / score table: f32 [V + 1, G·KP], columns ≥ K zero, row V = ``phi_oov``."""

@@ -23,7 +23,7 @@ from . import _lib
 
 __all__ = [
     "f32_keys", "i64_keys", "quantile_cuts", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
-    "sell_perm_z", "gibbs_pass", "foldin_pass", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "CountMode", "copy_rows", "score", "select_below", "choose_tiling",
+    "sell_perm_z", "gibbs_pass", "foldin_pass", "prior_rows", "theta_rows_prior", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "CountMode", "copy_rows", "score", "select_below", "choose_tiling",
 ]
 
 
@@ -546,7 +546,9 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
     ``ndk_src``) and adds the rows after the sweeps ≥ ``avg_from`` into ``ndk_sum``. A multi-chunk
     document's chunks add their Δ into ``ndk_dst`` (a pre-copied row of another buffer), one sweep
     a launch -- ``n_sweeps`` > 1 therefore needs ``select`` 1 -- and their window sums are the
-    caller's. CPU tensors run the oracle (:func:`oni355.ref.foldin_spec.foldin_pass`)."""
+    caller's. An optional ``st["prior"]`` (f32 [D, KS], :func:`prior_rows`) replaces α on the doc
+    side by the document's own row (the PRIOR instantiations of k_foldin); absent or None: the flat
+    prior α. CPU tensors run the oracle (:func:`oni355.ref.foldin_spec.foldin_pass`)."""
     from ..ref import foldin_spec
     if select not in (0, 1, 2):
         raise ValueError("select must be 0 (all), 1 (single-chunk docs) or 2 (multi-chunk docs)")
@@ -560,6 +562,11 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
     _check_layout(st, G, KS, ("phi", "ndk_src", "ndk_dst"))
     if st["ndk_sum"].shape != st["ndk_dst"].shape or st["ndk_sum"].dtype != torch.int32:
         raise ValueError("ndk_sum must be an int32 table of the doc rows' shape")
+    prior = st.get("prior")
+    if prior is not None:
+        _need(prior, torch.float32, "prior")
+        if prior.shape != st["ndk_dst"].shape or prior.device != st["ndk_dst"].device:
+            raise ValueError("prior must be an f32 table of the doc rows' shape, on their device")
     in_place = st["ndk_src"].data_ptr() == st["ndk_dst"].data_ptr()
     if select != 1 and not init and in_place and bool(st["chunk_multi"].any()):
         raise ValueError("multi-chunk documents add their deltas into a pre-copied row of another buffer")
@@ -567,12 +574,13 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
     if not _is_dev(st["tok_word"]):
         npst = _np_state(st, ("tok_word", "chunk_key"))
         cl = chunk_len.numpy()
+        pr = npst.get("prior")
         if init:
-            foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, True, 0, cl, select)
+            foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, True, 0, cl, select, prior=pr)
             return
         docs = npst["chunk_doc"][(npst["chunk_doc"] >= 0) & (npst["chunk_multi"] == 0)]
         for sweep in range(sweep_lo, sweep_lo + n_sweeps):
-            foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, False, sweep, cl, select)
+            foldin_spec.foldin_pass(npst, G, KP, K, alpha, s0, s1, False, sweep, cl, select, prior=pr)
             npst["ndk_src"] = npst["ndk_dst"]  # one launch: the rows stay with their unit
             if sweep >= avg_from and select != 2:
                 npst["ndk_sum"][docs] += npst["ndk_dst"][docs]
@@ -581,6 +589,7 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed: int, init
     _fill_ptrs(a, st, _SAMPLER_LAYOUT + ("phi", "ndk_sum"))
     a.n_slices, a.K, a.KS, a.alpha, a.seed0, a.seed1 = st["slice_len"].numel(), K, KS, float(alpha), s0, s1
     a.sweep_lo, a.n_sweeps, a.avg_from, a.select = int(sweep_lo), int(n_sweeps), int(avg_from), int(select)
+    a.prior = _lib.ptr(prior)  # None: the flat-α instantiations
     _lib.check(_lib.lib().oni_foldin_launch(C.byref(a), G, KP, 1 if init else 0, _lib.stream()), "oni_foldin_launch")
 
 
@@ -1058,6 +1067,54 @@ def theta_rows(n: torch.Tensor, K: int, add: float, den_add: float) -> torch.Ten
     out = torch.empty(D, KS, dtype=torch.float32, device=n.device)
     _lib.check(_lib.lib().oni_theta_rows(_lib.ptr(n), D, int(K), KS, float(np.float32(add)), float(np.float32(den_add)),
                                          _lib.ptr(out), _count_size(n), _lib.stream()), "oni_theta_rows")
+    return out
+
+
+def theta_rows_prior(ndk_sum: torch.Tensor, prior: torch.Tensor, K: int, S: float) -> torch.Tensor:
+    """θ under per-document prior rows (k_theta_rows_prior): (Σn_dj + S·pr_j)/(Σn_d + S·Σ_j pr_j) with
+    the f32 operation order of :func:`oni355.ref.foldin_spec.theta_rows_prior`, zero past K.
+    ``ndk_sum``: int32 or int64 [D, KS] window sums, ``prior`` f32 [D, KS]. CPU tensors run the oracle."""
+    from ..ref import foldin_spec
+    D, KS = ndk_sum.shape
+    _need(prior, torch.float32, "prior", D * KS)
+    _need(ndk_sum, ndk_sum.dtype, "ndk_sum")
+    if prior.shape != ndk_sum.shape or prior.device != ndk_sum.device:
+        raise ValueError("prior must be an f32 table of the doc rows' shape, on their device")
+    if not 1 <= K <= KS:
+        raise ValueError("K must be in [1, KS]")
+    csize = _count_size(ndk_sum)
+    if not _is_dev(ndk_sum):
+        return torch.from_numpy(foldin_spec.theta_rows_prior(ndk_sum.numpy(), prior.numpy(), int(K), float(S)))
+    out = torch.empty(D, KS, dtype=torch.float32, device=ndk_sum.device)
+    _lib.check(_lib.lib().oni_theta_rows_prior(_lib.ptr(ndk_sum), _lib.ptr(prior), D, int(K), KS,
+                                               float(np.float32(S)), _lib.ptr(out), csize, _lib.stream()),
+               "oni_theta_rows_prior")
+    return out
+
+
+def prior_rows(doc_keys_model: torch.Tensor, doc_theta: torch.Tensor, doc_tokens: torch.Tensor,
+               batch_doc_keys: torch.Tensor, K: int, KS: int, alpha: float, mass: float) -> torch.Tensor:
+    """Prior rows of a batch's documents from a saved model's document profiles (k_prior_rows), f32
+    [D, KS]: fma(min(tokens, mass), θ_train, α) for a document the model knows, α for every other
+    element (:func:`oni355.ref.foldin_spec.prior_rows`). ``doc_keys_model`` int64 [Dm] strictly
+    ascending, ``doc_theta`` f32 [Dm, K], ``doc_tokens`` int64 [Dm], ``batch_doc_keys`` int64 [D].
+    CPU tensors run the oracle."""
+    from ..ref import foldin_spec
+    Dm, D = int(doc_keys_model.numel()), int(batch_doc_keys.numel())
+    _need(doc_keys_model, torch.int64, "doc_keys_model")
+    _need(doc_tokens, torch.int64, "doc_tokens", Dm)
+    _need(batch_doc_keys, torch.int64, "batch_doc_keys")
+    _need(doc_theta, torch.float32, "doc_theta", Dm * int(K))
+    if not 1 <= K <= KS:
+        raise ValueError("K must be in [1, KS]")
+    if not _is_dev(batch_doc_keys):
+        return torch.from_numpy(foldin_spec.prior_rows(doc_keys_model.numpy(), doc_theta.numpy().reshape(Dm, K),
+                                                       doc_tokens.numpy(), batch_doc_keys.numpy(), int(K), int(KS),
+                                                       float(alpha), float(mass)))
+    out = torch.empty(D, KS, dtype=torch.float32, device=batch_doc_keys.device)
+    _lib.check(_lib.lib().oni_prior_rows(_lib.ptr(doc_keys_model), _lib.ptr(doc_theta), _lib.ptr(doc_tokens), Dm,
+                                         _lib.ptr(batch_doc_keys), D, int(K), int(KS), float(np.float32(alpha)),
+                                         float(np.float32(mass)), _lib.ptr(out), _lib.stream()), "oni_prior_rows")
     return out
 
 

@@ -56,6 +56,7 @@ class OniFoldin(C.Structure):
         ("ndk_src", vp), ("ndk_dst", vp), ("phi", vp), ("ndk_sum", vp),
         ("n_slices", i64), ("K", i32), ("KS", i32), ("alpha", f32), ("seed0", u32), ("seed1", u32),
         ("sweep_lo", i32), ("n_sweeps", i32), ("avg_from", i32), ("select", i32),
+        ("prior", vp),
     ]
 
 
@@ -84,6 +85,8 @@ _REGISTRY: dict[str, list] = {
     "oni_tail_sums": [vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                       vp, vp, vp],
     "oni_theta_rows": [vp, i64, C.c_int, C.c_int, f32, f32, vp, C.c_int, vp],
+    "oni_theta_rows_prior": [vp, vp, i64, C.c_int, C.c_int, f32, vp, C.c_int, vp],
+    "oni_prior_rows": [vp, vp, vp, i64, vp, i64, C.c_int, C.c_int, f32, f32, vp, vp],
     "oni_phi_rows": [vp, vp, i64, C.c_int, C.c_int, f32, f32, vp, C.c_int, C.c_int, vp],
     "oni_gibbs_apply": [vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, f32, f32, vp, C.c_int, C.c_int, C.c_int,
                         vp, vp, vp, i64, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp],

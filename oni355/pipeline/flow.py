@@ -342,11 +342,15 @@ def model_word_ids(word_keys64: torch.Tensor, vocab: torch.Tensor) -> tuple[torc
 def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
                seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
                feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
-               fuse: bool = True) -> FlowResult:
+               fuse: bool = True, prior_mass: float = 0.0) -> FlowResult:
     """Score a batch of flows against a saved model (``model``: models.saved.SavedModel) instead of
     training on it: words from the model's cuts, ids through its vocabulary (unseen words → the
     out-of-vocabulary row), the batch's own IP documents folded in against the frozen φ
-    (models.foldin.FoldIn), then the usual score plan / top-N against the model's table."""
+    (models.foldin.FoldIn), then the usual score plan / top-N against the model's table.
+
+    ``prior_mass`` > 0: an IP the model has a document profile of is folded in under the Dirichlet
+    prior α + min(its training tokens, prior_mass)·θ_train (ops.prior_rows) instead of the flat α, in
+    the draws and in θ; an IP the model does not know, and every IP at 0, behaves as without."""
     from ..models.corpus import auto_chunk_len, build_corpus
     from ..models.foldin import FoldIn
     from ..models.gibbs import tiling_for
@@ -356,6 +360,12 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
         raise ValueError(f"a {model.source} model cannot score flows")
     if feedback and log:
         log("analyst feedback is ignored when scoring against a saved model")
+    prior_mass = float(prior_mass)
+    if prior_mass < 0 or prior_mass != prior_mass:
+        raise ValueError("prior_mass must be ≥ 0")
+    if prior_mass > 0 and not model.has_docs:
+        raise ValueError("prior_mass > 0 needs a model saved with document profiles: save it with "
+                         "SavedModel.from_run(..., docs=True) (oni-ml --save-model without --no-model-docs)")
     timer = StageTimer(device)
     if device_cols is None:
         cols = with_ipv6_keys(cols, None)
@@ -387,8 +397,17 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
             pairs = oc.pair_build(inv, wids, D, V + 1, None, n0=int(n))
         corpus = build_corpus(inv, wids, D, V + 1, common.i64_to_u32bits(udoc), G, chunk_len, pairs=pairs)
         table = model.table(G, KP, dev)
+        prior, n_prior = None, 0
+        if prior_mass > 0:
+            mkeys = torch.from_numpy(model.doc_keys).to(dev)
+            prior = ops.prior_rows(mkeys, torch.from_numpy(model.doc_theta).to(dev),
+                                   torch.from_numpy(model.doc_tokens).to(dev), udoc.contiguous(), K, G * KP,
+                                   model.alpha, prior_mass)
+            if mkeys.numel():
+                pos = torch.searchsorted(mkeys, udoc).clamp_(max=int(mkeys.numel()) - 1)
+                n_prior = int(((mkeys[pos] == udoc) & (udoc < V6_KEY_BASE)).sum())
     with timer.stage("foldin"):
-        fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse)
+        fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
         fold.run(sweeps, avg_last)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     with timer.stage("score_prep"):
@@ -417,6 +436,8 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
     stats = corpus.stats()
     stats.update({"n_flows": n, "loglik": None, "mode": "infer", "n_oov_tokens": n_oov,
                   "foldin_launches": sum(fold.launches.values())})
+    if prior is not None:
+        stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
     stats.update({f"model_{k}": v for k, v in model.provenance.items() if isinstance(v, (int, float, str, bool))})
     return FlowResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), src_scores=parts[:, 0].numpy(),
                       dst_scores=parts[:, 1].numpy(), src_words=wparts[:, 0].numpy().view(np.uint32),

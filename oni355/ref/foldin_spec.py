@@ -21,13 +21,62 @@ from __future__ import annotations
 import numpy as np
 
 from . import spec
-from .spec import F32, U32, token_rand
+from .spec import F32, U32, fma_f32, token_rand
 
 SELECT_ALL, SELECT_SINGLE, SELECT_MULTI = 0, 1, 2
+# document keys from here up are ids of a per-day IPv6 dictionary (pipeline.flow.with_ipv6_keys):
+# they name another address on another day, so they carry no prior
+V6_KEY_BASE = 0xF0000000
+
+
+def prior_rows(doc_keys_model: np.ndarray, doc_theta: np.ndarray, doc_tokens: np.ndarray,
+               batch_doc_keys: np.ndarray, K: int, KS: int, alpha: float, mass: float) -> np.ndarray:
+    """Per-document Dirichlet prior rows of a batch from a saved model's document profiles
+    (k_prior_rows, csrc/kernels/foldin.hip), f32 [D, KS].
+
+    ``doc_keys_model`` int64 [Dm] strictly ascending, ``doc_theta`` f32 [Dm, ≥ K], ``doc_tokens``
+    int64 [Dm]; ``batch_doc_keys`` int64 [D]. A batch key found in the model (binary search) below
+    :data:`V6_KEY_BASE` gets pr_j = fma(m, θ_ij, f32(α)) for j < K with m = min(f32(tokens_i),
+    f32(mass)): the training day's θ weighted by at most ``mass`` pseudo-tokens, never by more than
+    the document had. Every other element (unknown keys, per-day IPv6 ids, columns ≥ K) is f32(α)."""
+    keys = np.asarray(batch_doc_keys, dtype=np.int64)
+    mk = np.asarray(doc_keys_model, dtype=np.int64)
+    a32 = F32(alpha)
+    out = np.full((keys.shape[0], KS), a32, dtype=F32)
+    if mk.shape[0] == 0 or keys.shape[0] == 0:
+        return out
+    pos = np.minimum(np.searchsorted(mk, keys), mk.shape[0] - 1)
+    hit = np.nonzero((mk[pos] == keys) & (keys < V6_KEY_BASE))[0]
+    row = pos[hit]
+    m = np.minimum(np.asarray(doc_tokens, dtype=np.int64)[row].astype(F32), F32(mass))
+    th = np.asarray(doc_theta, dtype=F32)[row, :K]
+    out[hit, :K] = fma_f32(np.broadcast_to(m[:, None], th.shape), th, np.full(th.shape, a32, dtype=F32))
+    return out
+
+
+def theta_rows_prior(ndk_sum: np.ndarray, prior: np.ndarray, K: int, S: float) -> np.ndarray:
+    """θ of documents folded in under per-document prior rows (k_theta_rows_prior,
+    csrc/kernels/day_tail.hip), f32 [D, KS]: with S32 = f32(S) window samples,
+    num_j = fma(S32, pr_j, f32(Σn_dj)), sp = pr_0 + pr_1 + … + pr_{K−1} added in that order in f32,
+    den = fma(S32, sp, f32(n_d)) with n_d the int64 row sum over j < K, θ_j = num_j / den; columns
+    ≥ K zero."""
+    n = np.asarray(ndk_sum)
+    pr = np.asarray(prior, dtype=F32)
+    D, KS = n.shape
+    S32 = np.full(D, F32(S), dtype=F32)
+    sp = np.zeros(D, dtype=F32)
+    for j in range(K):
+        sp = sp + pr[:, j]
+    nd = n[:, :K].astype(np.int64).sum(1).astype(F32)
+    den = fma_f32(S32, sp, nd)
+    th = np.zeros((D, KS), dtype=F32)
+    for j in range(K):
+        th[:, j] = fma_f32(S32, pr[:, j], n[:, j].astype(F32)) / den
+    return th
 
 
 def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, seed1: int, init: bool,
-                sweep: int, chunk_len: np.ndarray, select: int = SELECT_ALL) -> None:
+                sweep: int, chunk_len: np.ndarray, select: int = SELECT_ALL, prior: np.ndarray | None = None) -> None:
     """One init (``init``) or sweep pass over numpy state arrays, in place.
 
     Per chunk: ``n`` starts at zero (init) or at ``ndk_src[doc]``; tokens are taken in chunk order.
@@ -44,6 +93,9 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, see
     st keys: tok_word u32 (ids into φ, V = out of vocabulary), tok_z u8, slice_off i64, chunk_doc
     i32, chunk_pos0 i32, chunk_key u32, chunk_multi u8, ndk_src i32 [D, KS], ndk_dst i32 [D, KS],
     phi f32 [V + 1, KS] (columns ≥ K zero).
+
+    ``prior`` (f32 [D, KS], :func:`prior_rows`): a_j = f32(n_j) + prior[doc, j] in place of + f32(α),
+    the same row in every chunk of a document; nothing else changes.
     """
     S = 64 // G
     KS = G * KP
@@ -75,7 +127,8 @@ def foldin_pass(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, see
         if not init:
             zo = st["tok_z"][idx].astype(np.int64)
             n[act, zo] -= 1
-        av = (n[act].astype(F32) + alpha32).reshape(-1, G, KP)
+        add = alpha32 if prior is None else prior[doc[act]]
+        av = (n[act].astype(F32) + add).reshape(-1, G, KP)
         zn = spec.unit_draw(av, phi[w].reshape(-1, G, KP), rr, K)
         n[act, zn] += 1
         st["tok_z"][idx] = zn.astype(np.uint8)
@@ -96,18 +149,18 @@ def window(sweeps: int, avg_last: int) -> tuple[int, int]:
 
 
 def foldin_run(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, seed1: int, sweeps: int,
-               avg_last: int, chunk_len: np.ndarray):
+               avg_last: int, chunk_len: np.ndarray, prior: np.ndarray | None = None):
     """Init pass + ``sweeps`` sweeps (numbered 1..sweeps) over ``st`` (``ndk_src`` / ``ndk_dst``
     give the [D, KS] shape; their contents are replaced). Returns (ndk_sum, ndk): the sum of the
     doc rows after each of the last ``avg_last`` sweeps (int32 [D, KS]) and the final rows."""
     ndk = np.zeros_like(st["ndk_dst"])
     st["ndk_src"] = st["ndk_dst"] = ndk
-    foldin_pass(st, G, KP, K, alpha, seed0, seed1, True, 0, chunk_len)
+    foldin_pass(st, G, KP, K, alpha, seed0, seed1, True, 0, chunk_len, prior=prior)
     avg_from, _ = window(sweeps, avg_last)
     ndk_sum = np.zeros_like(ndk)
     for sweep in range(1, sweeps + 1):
         st["ndk_src"], st["ndk_dst"] = ndk, ndk.copy()  # multi-chunk rows: Δ into the pre-copied row
-        foldin_pass(st, G, KP, K, alpha, seed0, seed1, False, sweep, chunk_len)
+        foldin_pass(st, G, KP, K, alpha, seed0, seed1, False, sweep, chunk_len, prior=prior)
         ndk = st["ndk_dst"]
         if sweep >= avg_from:
             ndk_sum += ndk
@@ -117,4 +170,4 @@ def foldin_run(st: dict, G: int, KP: int, K: int, alpha: float, seed0: int, seed
     return ndk_sum, ndk
 
 
-__all__ = ["foldin_pass", "foldin_run", "window", "SELECT_ALL", "SELECT_SINGLE", "SELECT_MULTI", "spec"]
+__all__ = ["foldin_pass", "foldin_run", "window", "prior_rows", "theta_rows_prior", "V6_KEY_BASE", "SELECT_ALL", "SELECT_SINGLE", "SELECT_MULTI", "spec"]
