@@ -1163,8 +1163,10 @@ class GibbsLDA:
             return float(cw + host[0] - host[1] + (cd + host[2] - host[3]))
         nwk = self.nwk[:, :K].to(torch.float64)
         nk = self.nk_cur[:K].to(torch.float64)
+        # n_k + self.vbeta: the f32-rounded Vβ of the q table, which the device sums (ops.tail_sums)
+        # add too -- V * b in double moved this sum by ~1e-10 relative against the device's
         word = (K * (math.lgamma(V * b) - V * math.lgamma(b)) + torch.lgamma(nwk + b).sum()
-                - torch.lgamma(nk + V * b).sum())
+                - torch.lgamma(nk + self.vbeta).sum())
         D_own = self.c.D_own
         ndk = self.ndk_cur[:D_own, :K].to(torch.float64)
         nd = ndk.sum(1)

@@ -14,6 +14,8 @@ Behaviour spec sources (the reference has no readable source):
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 U32 = np.uint32
@@ -741,6 +743,58 @@ def score(theta, phi, d1, w1, d2=None, w2=None):
         return s1, s1, None
     s2 = dot_rows(theta[d2], phi[w2])
     return np.minimum(s1, s2).astype(F32), s1, s2
+
+
+# ------------------------------------------------------------------------------------------------
+# training tail (csrc/kernels/day_tail.hip): θ/φ rows, likelihood sums, health counts
+# ------------------------------------------------------------------------------------------------
+def theta_rows(n, K: int, add: float, den_add: float) -> np.ndarray:
+    """θ rows of k_theta_rows: (f32(n) + f32(add)) / (f32(n_d) + f32(den_add)), n_d the exact int64
+    sum of a row's first K counts rounded to f32 once, one f32 division; columns ≥ K are zero
+    (whatever they hold). ``n``: int32 or int64 [D, KS]."""
+    n = np.asarray(n)
+    nd = n[:, :K].astype(np.int64).sum(1)
+    den = nd.astype(F32) + F32(den_add)
+    with np.errstate(all="ignore"):  # the padding columns may hold anything
+        th = (n.astype(F32) + F32(add)) / den[:, None]
+    th[:, K:] = 0
+    return th.astype(F32)
+
+
+def phi_rows(nw, nk, K: int, add: float, vb: float) -> np.ndarray:
+    """φ rows of k_phi_rows: (f32(n_wk) + f32(add)) / (f32(n_k) + f32(vb)); columns ≥ K are zero.
+    ``nw``: int32 or int64 [V, KS], ``nk``: int32 or int64 [KS]."""
+    den = np.asarray(nk).astype(F32) + F32(vb)
+    with np.errstate(all="ignore"):
+        ph = (np.asarray(nw).astype(F32) + F32(add)) / den[None, :]
+    ph[:, K:] = 0
+    return ph.astype(F32)
+
+
+def tail_terms(nwk, nk, ndk, D: int, K: int, alpha: float, beta: float, vbeta: float) -> list:
+    """The lgamma terms of the four sums of :func:`tail_sums` (four lists of Python floats, in
+    row-major cell order): libm's lgamma of the double arguments k_tail_partials forms."""
+    nd_rows = np.asarray(ndk)[:D, :K]
+    nd = nd_rows.astype(np.int64).sum(1)  # exact: four counts of 2^30 give 2^32
+    args = (np.asarray(nwk)[:, :K].astype(np.float64) + beta, np.asarray(nk)[:K].astype(np.float64) + vbeta,
+            nd_rows.astype(np.float64) + alpha, nd.astype(np.float64) + float(K * alpha))
+    return [[math.lgamma(x) for x in a.ravel().tolist()] for a in args]
+
+
+def tail_sums(nwk, q, nk, ndk, D: int, K: int, alpha: float, beta: float, vbeta: float):
+    """What k_tail_partials / k_tail_final reduce, over the columns < K and the doc rows < D only.
+
+    Returns ``(sums, health, mags)``: ``sums`` = [Σlgamma(n_wk+β), Σlgamma(n_k+Vβ), Σlgamma(n_dk+α),
+    Σlgamma(n_d+Kα)], each the correctly rounded sum (math.fsum) of the double terms of
+    :func:`tail_terms`; ``health`` = [#non-finite q, #negative n_wk or n_k, #negative n_dk], exact
+    integers; ``mags`` = Σ|term| of each of the four sums (the scale of a summation error)."""
+    terms = tail_terms(nwk, nk, ndk, D, K, alpha, beta, vbeta)
+    sums = [math.fsum(t) for t in terms]
+    mags = [math.fsum(abs(x) for x in t) for t in terms]
+    nwk, q, nk, ndk = (np.asarray(a) for a in (nwk, q, nk, ndk))
+    health = [int((~np.isfinite(q[:, :K])).sum()), int((nwk[:, :K] < 0).sum()) + int((nk[:K] < 0).sum()),
+              int((ndk[:D, :K] < 0).sum())]
+    return sums, health, mags
 
 
 # ------------------------------------------------------------------------------------------------
