@@ -40,12 +40,12 @@ def main() -> int:
     ap.add_argument("--variants", default="train,infer,unfused,prior")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--source", choices=["flow", "dns", "proxy"], default="flow",
+                    help="the day's source (--flows events; --topics is 20 unless given: pass 50 for a default dns day)")
     a = ap.parse_args()
     import torch
 
     from oni355.models.saved import SavedModel
-    from oni355.pipeline.flow import run_flow, score_flow
-    from oni355.synth.flow import generate_flows
 
     dev = torch.device(a.device)
 
@@ -53,12 +53,33 @@ def main() -> int:
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    day = generate_flows(a.flows, seed=a.seed, n_hosts=max(64, a.flows // 25))
-    print(f"generated {a.flows} flows in {time.perf_counter() - t0:.1f} s", flush=True)
     kw = dict(tol=1.0, maxresults=3000, device=dev)
+    if a.source == "flow":
+        from oni355.pipeline.flow import run_flow, score_flow
+        from oni355.synth.flow import generate_flows
+        day = generate_flows(a.flows, seed=a.seed, n_hosts=max(64, a.flows // 25))
+    elif a.source == "dns":
+        from oni355.pipeline import dns
+        from oni355.synth.dns import generate_dns
+        day = generate_dns(a.flows, seed=a.seed, user_domain="intel")
+
+        def run_flow(cols, **k):
+            return dns.run_dns(cols, user_domain="intel", **k)
+        score_flow = dns.score_dns
+    else:
+        from oni355.pipeline import proxy
+        from oni355.synth.proxy import generate_proxy
+        day = generate_proxy(a.flows, seed=a.seed)
+        run_flow, score_flow = proxy.run_proxy, proxy.score_proxy
+    print(f"generated {a.flows} {a.source} events in {time.perf_counter() - t0:.1f} s", flush=True)
     # the model is trained once (this untimed day is also the warm-up of the training variant)
     first = run_flow(day.cols, K=a.topics, sweeps=a.sweeps, **kw)
-    model = SavedModel.from_run(first.lda, first.cuts, "flow", {"day": "bench"})
+    if a.source == "flow":
+        model = SavedModel.from_run(first.lda, first.cuts, "flow", {"day": "bench"})
+    elif a.source == "dns":
+        model = dns.model_from_result(first, None, "intel", {"day": "bench"})
+    else:
+        model = proxy.model_from_result(first, None, {"day": "bench"})
     with tempfile.TemporaryDirectory() as td:
         model_bytes = {"with_docs": os.path.getsize(model.save(os.path.join(td, "m.npz"))),
                        "without_docs": os.path.getsize(model.without_docs().save(os.path.join(td, "m0.npz")))}
@@ -88,6 +109,9 @@ def main() -> int:
                 line["ms_per_sweep"] = round(t.get("train_dev_s", t.get("train_s", 0.0)) / a.sweeps * 1e3, 4)
             else:
                 line["ms_per_sweep"] = round(t.get("foldin_dev_s", t.get("foldin_s", 0.0)) / max(a.infer_sweeps, 1) * 1e3, 4)
+                # the stage that maps the batch's words into the model's vocabulary
+                line["vocab_ms"] = round(t.get("vocab_dev_s", t.get("vocab_s", 0.0)) * 1e3, 4)
+                line["vocab_wall_ms"] = round(t.get("vocab_s", 0.0) * 1e3, 4)  # host time of the stage
                 line["launches"] = res.stats["foldin_launches"]
                 if name == "prior":
                     line["n_prior_docs"] = res.stats["n_prior_docs"]
@@ -98,11 +122,16 @@ def main() -> int:
 
     def summ(v):
         d, s = [x["day_ms"] for x in v], [x["ms_per_sweep"] for x in v]
-        return {"day_ms_median": statistics.median(d), "day_ms_min": min(d), "day_ms_spread": round(max(d) - min(d), 2),
-                "ms_per_sweep_median": statistics.median(s), "ms_per_sweep_min": min(s),
-                "ms_per_sweep_spread": round(max(s) - min(s), 4)}
+        out = {"day_ms_median": statistics.median(d), "day_ms_min": min(d), "day_ms_spread": round(max(d) - min(d), 2),
+               "ms_per_sweep_median": statistics.median(s), "ms_per_sweep_min": min(s),
+               "ms_per_sweep_spread": round(max(s) - min(s), 4)}
+        if all("vocab_ms" in x for x in v):
+            vo = [x["vocab_ms"] for x in v]
+            out.update({"vocab_ms_median": statistics.median(vo), "vocab_ms_min": min(vo),
+                        "vocab_ms_spread": round(max(vo) - min(vo), 4)})
+        return out
     summary = {n: summ(v) for n, v in days.items()}
-    out = {"flows": a.flows, "topics": a.topics, "train_sweeps": a.sweeps, "infer_sweeps": a.infer_sweeps,
+    out = {"source": a.source, "flows": a.flows, "topics": a.topics, "train_sweeps": a.sweeps, "infer_sweeps": a.infer_sweeps,
            "avg_last": a.avg_last, "rounds": a.rounds, "prior_mass": a.prior_mass, "model_bytes": model_bytes,
            "summary": summary, "days": days}
     print(json.dumps({"summary": summary}), flush=True)

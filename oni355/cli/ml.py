@@ -248,9 +248,6 @@ def main(argv=None) -> int:
     gpus_asked = a.gpus if a.gpus is not None else cfg.PROCESS_COUNT
     if a.model or a.save_model:
         opt = "--model" if a.model else "--save-model"
-        if a.source != "flow":
-            raise SystemExit(f"oni-ml: {opt} supports flow only: {a.source} words depend on per-day dictionaries "
-                             "(saved-model scoring for dns / proxy is a follow-up)")
         if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
     if a.model:
@@ -261,6 +258,14 @@ def main(argv=None) -> int:
             raise SystemExit(f"oni-ml: --model {a.model}: no such file")
         if a.infer_prior_mass < 0:
             raise SystemExit("oni-ml: --infer-prior-mass must be ≥ 0")
+        from ..models.saved import model_source
+        try:
+            msrc = model_source(a.model)
+        except Exception as e:
+            raise SystemExit(f"oni-ml: --model {a.model}: {e}")
+        if msrc != a.source:
+            raise SystemExit(f"oni-ml: --model {a.model}: a {msrc} model cannot score {a.source} events: each "
+                             "source's words come from its own cuts and per-day dictionaries")
     if a.max_restarts > 0 and os.environ.get("ONI_SUPERVISED") != "1":
         if inside:
             # the supervisor's children would write to the service's stdout, not the client's
@@ -319,16 +324,23 @@ def main(argv=None) -> int:
                          ldac_lag=a.ldac_lag)
     if a.model:
         from ..models.saved import SavedModel
-        from ..pipeline.flow import score_flow
         model = SavedModel.load(a.model)
         log(f"model {a.model}: K={model.K}, V={model.V}, trained {model.provenance}")
         if a.infer_prior_mass > 0 and not model.has_docs:
             raise SystemExit(f"oni-ml: --infer-prior-mass needs per-IP topic profiles, which {a.model} was saved "
                              "without: save the model again with --save-model and no --no-model-docs")
-        res = score_flow(cols, model, tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps,
-                         avg_last=a.infer_avg_last, seed=cfg.SEED, device=device, comm=comm, feedback=fb,
-                         chunk_len=cfg.CHUNK_LEN, row_offset=row_off, log=log,
-                         prior_mass=a.infer_prior_mass)
+        score_kw = dict(tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps, avg_last=a.infer_avg_last,
+                        seed=cfg.SEED, device=device, comm=comm, feedback=fb, chunk_len=cfg.CHUNK_LEN,
+                        row_offset=row_off, log=log, prior_mass=a.infer_prior_mass)
+        if a.source == "flow":
+            from ..pipeline.flow import score_flow
+            res = score_flow(cols, model, **score_kw)
+        elif a.source == "dns":
+            from ..pipeline.dns import score_dns
+            res = score_dns(cols, model, top_domains=top, user_domain=cfg.USER_DOMAIN, **score_kw)
+        else:
+            from ..pipeline.proxy import score_proxy
+            res = score_proxy(cols, model, top_domains=top, **score_kw)
     elif a.source == "flow":
         from ..pipeline.flow import run_flow
         res = run_flow(cols, **common_kw)
@@ -341,9 +353,21 @@ def main(argv=None) -> int:
     elif a.source == "dns":
         from ..pipeline.dns import run_dns
         res = run_dns(cols, top_domains=top, user_domain=cfg.USER_DOMAIN, **common_kw)
+        if a.save_model:
+            from ..pipeline.dns import model_from_result
+            os.makedirs(a.save_model, exist_ok=True)
+            mp = model_from_result(res, top, cfg.USER_DOMAIN, {"day": a.date}, docs=not a.no_model_docs).save(
+                os.path.join(a.save_model, "dns_model.npz"))
+            log(f"saved model -> {mp}")
     else:
         from ..pipeline.proxy import run_proxy
         res = run_proxy(cols, top_domains=top, **common_kw)
+        if a.save_model:
+            from ..pipeline.proxy import model_from_result
+            os.makedirs(a.save_model, exist_ok=True)
+            mp = model_from_result(res, top, {"day": a.date}, docs=not a.no_model_docs).save(
+                os.path.join(a.save_model, "proxy_model.npz"))
+            log(f"saved model -> {mp}")
     rendered = rio.render_result(a.source, cols, res, row_off, comm)
     out = None
     if rank == 0:

@@ -17,7 +17,13 @@ import torch
 from ..ref.foldin_spec import V6_KEY_BASE  # keys from here up are per-day IPv6 ids: never saved
 
 FORMAT = 1
-_ARRAYS = ("vocab", "phi", "phi_oov", "cuts_time", "cuts_ibyt", "cuts_ipkt")
+_BASE_ARRAYS = ("vocab", "phi", "phi_oov")
+# the cut lists every source's words are made with (the BINNED names of pipeline/dns.py, proxy.py)
+CUT_NAMES = {"flow": ("time", "ibyt", "ipkt"),
+             "dns": ("frame_len", "time", "sub_len", "sub_ent", "periods"),
+             "proxy": ("time", "ua_freq", "uri_ent", "uri_len")}
+# a proxy model's user-agent frequency table (pipeline.proxy.featurize): both or none elsewhere
+_UA_ARRAYS = ("ua_keys", "ua_counts")
 # the optional document profiles: all three or none. An older build's loader ignores them.
 _DOC_ARRAYS = ("doc_keys", "doc_theta", "doc_tokens")
 
@@ -39,6 +45,42 @@ def oov_row(model) -> np.ndarray:
     return (num / den).astype(f32)
 
 
+def _cut_array(name: str, v) -> np.ndarray:
+    """One cut list as saved: the integer values ``common.binned_cuts`` / ``FlowCuts`` return, kept
+    exactly. They are u32 order keys (of f32 features) or raw counts: uint32 where every value fits
+    (every cut of this code base does; flow cuts therefore stay uint32), else int64."""
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"cuts[{name!r}] must be integers (raw order keys), got {a.dtype}")
+    a = a.reshape(-1)
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        return np.ascontiguousarray(a, dtype=np.int64)
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def model_source(path: str) -> str:
+    """The source (``flow``, ``dns``, ``proxy``) a saved model file was trained on; reads only the
+    file's meta record."""
+    with np.load(path, allow_pickle=False) as z:
+        if "meta" not in z.files:
+            raise ValueError("not a saved oni355 model (missing ['meta'])")
+        return str(json.loads(str(z["meta"][0])).get("source"))
+
+
+def _host(t) -> np.ndarray:
+    return t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def top_digest(domains) -> tuple[int, str]:
+    """(entries, digest) of a top-domain list as :func:`oni355.pipeline.dns.top_set` reads it
+    (stripped, lower case, empty lines dropped, order kept); (0, "") without a list."""
+    import hashlib
+    names = [d.strip().lower() for d in (domains or []) if d.strip()]
+    if not names:
+        return 0, ""
+    return len(names), hashlib.sha256("\n".join(names).encode()).hexdigest()[:16]
+
+
 @dataclass
 class SavedModel:
     source: str
@@ -48,12 +90,15 @@ class SavedModel:
     vocab: np.ndarray      # int64 [V] sorted word keys (row i of phi)
     phi: np.ndarray        # f32 [V, K]
     phi_oov: np.ndarray    # f32 [K] row of a word the model never saw
-    cuts: dict             # feature cuts as raw key arrays (flow: time / ibyt / ipkt, uint32)
+    cuts: dict             # feature cuts as raw key arrays, by name (:data:`CUT_NAMES` of the source)
     provenance: dict = field(default_factory=dict)
     # the training day's document profiles (all three or none)
     doc_keys: np.ndarray | None = None     # int64 [Dm] strictly ascending document (IP) keys
     doc_theta: np.ndarray | None = None    # f32 [Dm, K] θ of each document at the end of training
     doc_tokens: np.ndarray | None = None   # int64 [Dm] training tokens of each document
+    # a proxy model's user-agent frequency table of the training day (both; no other source has one)
+    ua_keys: np.ndarray | None = None      # int64 [U] strictly ascending (signed) user-agent hashes
+    ua_counts: np.ndarray | None = None    # int64 [U] events of the training day with that user agent
 
     @property
     def V(self) -> int:
@@ -71,7 +116,20 @@ class SavedModel:
         self.vocab = np.ascontiguousarray(self.vocab, dtype=np.int64)
         self.phi = np.ascontiguousarray(self.phi, dtype=np.float32)
         self.phi_oov = np.ascontiguousarray(self.phi_oov, dtype=np.float32)
-        self.cuts = {k: np.ascontiguousarray(v, dtype=np.uint32) for k, v in self.cuts.items()}
+        self.cuts = {k: _cut_array(k, v) for k, v in self.cuts.items()}
+        missing = [k for k in CUT_NAMES.get(self.source, ()) if k not in self.cuts]
+        if missing:
+            raise ValueError(f"a {self.source} model needs the cuts {missing}")
+        ua = [getattr(self, k) is not None for k in _UA_ARRAYS]
+        if any(ua) != (self.source == "proxy") or any(ua) != all(ua):
+            raise ValueError("ua_keys and ua_counts come together, with a proxy model and no other")
+        if all(ua):
+            self.ua_keys = np.ascontiguousarray(self.ua_keys, dtype=np.int64)
+            self.ua_counts = np.ascontiguousarray(self.ua_counts, dtype=np.int64)
+            if self.ua_keys.ndim != 1 or self.ua_counts.shape != self.ua_keys.shape:
+                raise ValueError("ua_keys must be [U] and ua_counts [U]")
+            if self.ua_keys.shape[0] > 1 and not bool((self.ua_keys[1:] > self.ua_keys[:-1]).all()):
+                raise ValueError("ua_keys must be strictly ascending (signed) user-agent hashes")
         if self.phi.shape != (self.V, self.K) or self.phi_oov.shape != (self.K,):
             raise ValueError(f"phi must be [V={self.V}, K={self.K}] and phi_oov [K]")
         if self.V > 1 and not bool((self.vocab[1:] > self.vocab[:-1]).all()):
@@ -90,11 +148,14 @@ class SavedModel:
                 raise ValueError("doc_keys must be strictly ascending document keys")
 
     @classmethod
-    def from_run(cls, run, cuts, source: str, cfg: dict | None = None, docs: bool = True) -> "SavedModel":
+    def from_run(cls, run, cuts, source: str, cfg: dict | None = None, docs: bool = True,
+                 ua_table: tuple | None = None) -> "SavedModel":
         """The model of a finished training run (``run``: pipeline.common.LdaRun; ``cuts``: the
-        day's FlowCuts; ``cfg``: provenance such as the training day). ``docs``: keep the day's
-        document profiles (θ as scoring read it, and each document's token count), without the
-        documents keyed by the day's IPv6 dictionary."""
+        day's cuts as a name → values mapping, or a flow day's FlowCuts; ``cfg``: provenance such
+        as the training day, the top-domain list's size and digest, the user domain). ``docs``:
+        keep the day's document profiles (θ as scoring read it, and each document's token count),
+        without the documents keyed by the day's IPv6 dictionary. ``ua_table``: a proxy day's
+        (sorted user-agent hashes, counts) as ``pipeline.proxy.featurize`` returns it."""
         from ..utils import provenance as prov
         m = run.model
         if run.route is not None or run.extra_models:
@@ -111,9 +172,15 @@ class SavedModel:
             keep = dkeys < V6_KEY_BASE
             prof = {"doc_keys": dkeys[keep], "doc_theta": theta[:, :K].cpu().numpy()[keep],
                     "doc_tokens": run.corpus.doc_lengths()[: dkeys.shape[0]].cpu().numpy().astype(np.int64)[keep]}
+        if hasattr(cuts, "ibyt"):  # a flow day's FlowCuts
+            cuts = {"time": cuts.time, "ibyt": cuts.ibyt, "ipkt": cuts.ipkt}
+        else:
+            cuts = {k: np.asarray(v) for k, v in cuts.items()}
+        if ua_table is not None:
+            prof.update(ua_keys=_host(ua_table[0]), ua_counts=_host(ua_table[1]))
         return cls(source=source, K=K, alpha=float(m.alpha), beta=float(m.beta),
                    vocab=run.vocab.cpu().numpy(), phi=m.phi()[:, :K].cpu().numpy(), phi_oov=oov_row(m),
-                   cuts={"time": cuts.time, "ibyt": cuts.ibyt, "ipkt": cuts.ipkt}, provenance=prv, **prof)
+                   cuts=cuts, provenance=prv, **prof)
 
     def save(self, path: str) -> str:
         meta = {"format": FORMAT, "source": self.source, "K": int(self.K), "alpha": float(self.alpha),
@@ -121,6 +188,8 @@ class SavedModel:
         if not path.endswith(".npz"):
             path += ".npz"
         docs = {k: getattr(self, k) for k in _DOC_ARRAYS} if self.has_docs else {}
+        if self.ua_keys is not None:
+            docs.update({k: getattr(self, k) for k in _UA_ARRAYS})
         with open(path, "wb") as f:
             np.savez(f, meta=np.array([json.dumps(meta, sort_keys=True)]), vocab=self.vocab, phi=self.phi,
                      phi_oov=self.phi_oov, **{f"cuts_{k}": v for k, v in self.cuts.items()}, **docs)
@@ -129,17 +198,27 @@ class SavedModel:
     @classmethod
     def load(cls, path: str) -> "SavedModel":
         with np.load(path, allow_pickle=False) as z:
-            missing = [k for k in ("meta", *_ARRAYS) if k not in z.files]
+            missing = [k for k in ("meta", *_BASE_ARRAYS) if k not in z.files]
             if missing:
                 raise ValueError(f"{path}: not a saved oni355 model (missing {missing})")
             meta = json.loads(str(z["meta"][0]))
             if meta.get("format") != FORMAT:
                 raise ValueError(f"{path}: model format {meta.get('format')} (this build reads {FORMAT})")
-            arr = {k: z[k] for k in _ARRAYS}
+            source = meta["source"]
+            if source not in CUT_NAMES:
+                raise ValueError(f"{path}: a model of the unknown source {source!r}")
+            need = [f"cuts_{k}" for k in CUT_NAMES[source]] + (list(_UA_ARRAYS) if source == "proxy" else [])
+            missing = [k for k in need if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: not a saved {source} model (missing {missing})")
+            arr = {k: z[k] for k in _BASE_ARRAYS}
+            cuts = {k[5:]: z[k] for k in need if k.startswith("cuts_")}
             docs = {k: z[k] for k in _DOC_ARRAYS if k in z.files}
-        return cls(source=meta["source"], K=int(meta["K"]), alpha=float(meta["alpha"]), beta=float(meta["beta"]),
+            if source == "proxy":
+                docs.update({k: z[k] for k in _UA_ARRAYS})
+        return cls(source=source, K=int(meta["K"]), alpha=float(meta["alpha"]), beta=float(meta["beta"]),
                    vocab=arr["vocab"], phi=arr["phi"], phi_oov=arr["phi_oov"],
-                   cuts={k[5:]: arr[k] for k in _ARRAYS if k.startswith("cuts_")}, provenance=meta.get("provenance", {}), **docs)
+                   cuts=cuts, provenance=meta.get("provenance", {}), **docs)
 
     def table(self, G: int, KP: int, device) -> torch.Tensor:
         """The sampler / score table: f32 [V + 1, G·KP], columns ≥ K zero, row V = ``phi_oov``."""

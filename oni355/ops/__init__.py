@@ -23,7 +23,7 @@ from . import _lib
 
 __all__ = [
     "f32_keys", "i64_keys", "quantile_cuts", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
-    "sell_perm_z", "gibbs_pass", "foldin_pass", "prior_rows", "theta_rows_prior", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "CountMode", "copy_rows", "score", "select_below", "choose_tiling",
+    "sell_perm_z", "gibbs_pass", "foldin_pass", "prior_rows", "theta_rows_prior", "table_lookup", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "CountMode", "copy_rows", "score", "select_below", "choose_tiling",
 ]
 
 
@@ -1116,6 +1116,41 @@ def prior_rows(doc_keys_model: torch.Tensor, doc_theta: torch.Tensor, doc_tokens
                                          _lib.ptr(batch_doc_keys), D, int(K), int(KS), float(np.float32(alpha)),
                                          float(np.float32(mass)), _lib.ptr(out), _lib.stream()), "oni_prior_rows")
     return out
+
+
+def table_lookup(keys: torch.Tensor, queries: torch.Tensor, values: torch.Tensor | None = None,
+                 misses: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Every query's entry in a sorted table (k_table_lookup): ``keys`` int64 [M] strictly ascending
+    (signed order), ``queries`` int64 [n]. Id mode (``values`` None): int32 position of each query in
+    ``keys``, M on a miss. Value mode (``values`` int64 [M]): int32 min(values[pos], 2^31 − 1), 0 on a
+    miss. Returns (out int32 [n], the miss counter: int64 [1] on the queries' device). The number
+    of misses is ADDED to ``misses`` when one is given (else to a fresh zero); nothing here waits
+    for the device, the caller reads the counter when it next reads results. CPU tensors run the
+    oracle (:func:`oni355.ref.lookup_spec.table_lookup`)."""
+    from ..ref import lookup_spec
+    M, n = int(keys.numel()), int(queries.numel())
+    _need(keys, torch.int64, "keys")
+    _need(queries, torch.int64, "queries")
+    if values is not None:
+        _need(values, torch.int64, "values", M)
+    if M > lookup_spec.I32_MAX:
+        raise ValueError("table_lookup: at most 2^31 - 1 keys")
+    dev = queries.device
+    if keys.device != dev or (values is not None and values.device != dev):
+        raise ValueError("table_lookup: the table and the queries must be on one device")
+    if misses is None:
+        misses = torch.zeros(1, dtype=torch.int64, device=dev)
+    _need(misses, torch.int64, "misses", 1)
+    if misses.device != dev:
+        raise ValueError("table_lookup: the miss counter must be on the queries' device")
+    if not _is_dev(queries):
+        out, miss = lookup_spec.table_lookup(keys.numpy(), queries.numpy(), None if values is None else values.numpy())
+        misses += miss
+        return torch.from_numpy(out), misses
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().oni_table_lookup(_lib.ptr(keys), _lib.ptr(values), M, _lib.ptr(queries), n, _lib.ptr(out),
+                                           _lib.ptr(misses), _lib.stream()), "oni_table_lookup")
+    return out, misses
 
 
 def phi_rows(nw: torch.Tensor, nk: torch.Tensor, K: int, add: float, vb: float) -> torch.Tensor:

@@ -104,6 +104,7 @@ _REGISTRY: dict[str, list] = {
     "oni_wdelta_recount": [vp, vp, vp, i64, vp, C.c_int, C.c_int, vp],
     "oni_foldin_launch": [C.POINTER(OniFoldin), C.c_int, C.c_int, C.c_int, vp],
     "oni_foldin_sizeof_args": [],
+    "oni_table_lookup": [vp, vp, i64, vp, i64, vp, vp, vp],
 }
 # argument structs whose size the library reports: checked against the mirrors above at load
 _ARG_STRUCTS = {"oni_gibbs_sizeof_args": OniGibbs, "oni_mh_sizeof_args": OniMH, "oni_foldin_sizeof_args": OniFoldin}

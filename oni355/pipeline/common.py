@@ -1053,6 +1053,114 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
                         words=words.cpu().numpy().view(np.uint64), timings=t, stats=stats, lda=run)
 
 
+def model_word_ids(word_keys64: torch.Tensor, vocab: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(int32 id of every word key in the saved model's sorted ``vocab``, the device counter of the
+    keys absent from it: int64 [1]): an absent word gets id V, the table's out-of-vocabulary row.
+    One lookup kernel (ops.table_lookup) and no host read: the caller reads the counter with its
+    result rows."""
+    return ops.table_lookup(vocab.contiguous(), word_keys64.contiguous())
+
+
+def check_prior_mass(prior_mass: float, model) -> float:
+    prior_mass = float(prior_mass)
+    if prior_mass < 0 or prior_mass != prior_mass:
+        raise ValueError("prior_mass must be ≥ 0")
+    if prior_mass > 0 and not model.has_docs:
+        raise ValueError("prior_mass > 0 needs a model saved with document profiles: save it with "
+                         "SavedModel.from_run(..., docs=True) (oni-ml --save-model without --no-model-docs)")
+    return prior_mass
+
+
+def top_list_mismatch(model, top_domains, user_domain: str | None, log=None) -> bool:
+    """Does the top-domain list (or, with ``user_domain`` not None, the user domain) of this scoring
+    run differ from what the model's provenance records of its training day? Allowed (the words of
+    the affected events change, nothing else), but said once."""
+    from ..models.saved import top_digest
+    n, dg = top_digest(top_domains)
+    p = model.provenance
+    bad = []
+    if (int(p.get("top_entries", 0)), str(p.get("top_digest", ""))) != (n, dg):
+        bad.append(f"a top-domain list of {n} entries (digest {dg or '-'}) where the model was trained with "
+                   f"{p.get('top_entries', 0)} (digest {p.get('top_digest') or '-'})")
+    if user_domain is not None and str(p.get("user_domain", "")) != user_domain:
+        bad.append(f"user domain {user_domain!r} where the model was trained with {p.get('user_domain', '')!r}")
+    if bad and log:
+        log("scoring with " + " and ".join(bad) + ": the affected events are worded differently from the model's day")
+    return bool(bad)
+
+
+@traced("oni:score_single_doc_events")
+def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, model, tol: float, maxresults: int,
+                            sweeps: int, avg_last: int, seed: int, chunk_len: int, row_offset: int,
+                            timer: StageTimer, fuse: bool = True, prior_mass: float = 0.0) -> SingleResult:
+    """The DNS / proxy half of scoring against a saved model, after wordification: one (doc, word)
+    token per event. Word ids through the model's vocabulary (an unseen word → id V, the
+    out-of-vocabulary row), the batch's own documents folded in against the frozen table
+    (models.foldin.FoldIn, optionally under per-IP priors), θ, then the one-sided score plan and
+    top-N against the model's table -- :func:`oni355.pipeline.flow.score_flow` for one endpoint."""
+    from ..models.foldin import FoldIn
+    from ..models.gibbs import tiling_for
+    from ..ref.foldin_spec import V6_KEY_BASE
+    dev = doc_keys64.device
+    n = int(doc_keys64.numel())
+    with timer.stage("vocab"):
+        vocab = torch.from_numpy(model.vocab).to(dev)
+        V = int(vocab.numel())
+        wids, oov = model_word_ids(word_keys64, vocab)
+    with timer.stage("corpus"):
+        K = int(model.K)
+        G, KP = tiling_for(K, "dense")
+        if chunk_len <= 0:
+            chunk_len = auto_chunk_len(n, G)
+        udoc, inv = encode_docs(doc_keys64.contiguous())
+        D = int(udoc.numel())
+        pairs = None
+        if dev.type == "cuda":
+            from ..ops import corpus as oc
+            pairs = oc.pair_build(inv, wids, D, V + 1, None, n0=n)
+        corpus = build_corpus(inv, wids, D, V + 1, i64_to_u32bits(udoc), G, chunk_len, pairs=pairs)
+        table = model.table(G, KP, dev)
+        prior, n_prior = None, 0
+        if prior_mass > 0:
+            mkeys = torch.from_numpy(model.doc_keys).to(dev)
+            prior = ops.prior_rows(mkeys, torch.from_numpy(model.doc_theta).to(dev),
+                                   torch.from_numpy(model.doc_tokens).to(dev), udoc.contiguous(), K, G * KP,
+                                   model.alpha, prior_mass)
+            if mkeys.numel():
+                pos = torch.searchsorted(mkeys, udoc).clamp_(max=int(mkeys.numel()) - 1)
+                n_prior = int(((mkeys[pos] == udoc) & (udoc < V6_KEY_BASE)).sum())
+    with timer.stage("foldin"):
+        fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
+        fold.run(sweeps, avg_last)
+    hist = torch.zeros(2048, dtype=torch.int32, device=dev)
+    with timer.stage("score_prep"):
+        theta = fold.theta()
+        if pairs is not None and not SCORE_TILES:
+            plan = plan_from_pairs(pairs, n, 1)
+        else:
+            # the torch reference plan over (doc row, word id) pairs (score_plan looks word KEYS up
+            # in the vocabulary, which unseen words are not in)
+            uniq, pinv = torch.unique(inv.to(torch.int64) * (V + 1) + wids.to(torch.int64), return_inverse=True)
+            plan = ScorePlan((uniq // (V + 1)).to(torch.int32).contiguous(),
+                             (uniq % (V + 1)).to(torch.int32).contiguous(), [pinv.to(torch.int32).contiguous()])
+    with timer.stage("score"):
+        score, _, _ = plan_score(theta, table, plan, tol, hist=hist)
+        rows, scs = top_n(score, tol, maxresults, None, row_offset, hist=hist, order=plan.order)
+    t = timer.summary()
+    t["records_scored"] = n
+    t["sweeps"] = int(sweeps)
+    # the result rows' words and the miss counter come to the host together
+    words = word_keys64[(rows - row_offset).to(dev)].cpu()
+    stats = corpus.stats()
+    stats.update({"events": n, "loglik": None, "mode": "infer", "n_oov_tokens": int(oov.item()),
+                  "foldin_launches": sum(fold.launches.values())})
+    if prior is not None:
+        stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
+    stats.update({f"model_{k}": v for k, v in model.provenance.items() if isinstance(v, (int, float, str, bool))})
+    return SingleResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), words=words.numpy().view(np.uint64),
+                        timings=t, stats=stats, lda=fold)
+
+
 def rows_in_order(gid_all: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
     """Index of every id of ``rows`` in ``gid_all`` (a permutation of the same distinct ids)."""
     o = torch.argsort(gid_all)

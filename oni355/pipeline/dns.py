@@ -93,7 +93,9 @@ def time_keys(unix: torch.Tensor) -> torch.Tensor:
 
 
 @traced("oni:dns.featurize")
-def featurize(d: dict, comm: Comm | None, topset: HashSet | None, user_domain: str):
+def featurize(d: dict, comm: Comm | None, topset: HashSet | None, user_domain: str, cuts: dict | None = None):
+    """(words, cuts, features). ``cuts``: word the rows with these cut lists (a saved model's)
+    instead of the quantiles of the rows themselves."""
     rh, top, sub_len, sub_ent, per = sops.domain_features(d["name_off"], d["name_chars"], topset, user_domain)
     keys = {"frame_len": d["frame_len"], "time": time_keys(d["unix_tstamp"]), "sub_len": sub_len,
             "sub_ent": ops.f32_keys(sub_ent), "periods": per}
@@ -101,7 +103,10 @@ def featurize(d: dict, comm: Comm | None, topset: HashSet | None, user_domain: s
     n_glob = n
     if comm is not None and comm.dist:
         n_glob = int(comm.allreduce_np(np.array([n], np.int64))[0])
-    cuts, dev_cuts = common.binned_cuts(keys, BINNED, comm, n_glob)
+    if cuts is not None:
+        dev_cuts = None
+    else:
+        cuts, dev_cuts = common.binned_cuts(keys, BINNED, comm, n_glob)
     words = sops.pack_words([keys[name].contiguous() for name, _, _ in BINNED],
                             [range(len(fr)) if dev_cuts is not None else cuts[name] for name, fr, _ in BINNED],
                             [s for _, _, s in BINNED], [d[name] for name, _, _ in RAW], [m for _, m, _ in RAW],
@@ -143,5 +148,51 @@ def run_dns(cols: dict, K: int = 50, sweeps: int = 200, tol: float = 1.0, maxres
                                        timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag,
                                        key_bits=40)
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in cuts.items()}
+    res.stats["features"] = feats
+    return res
+
+
+def model_from_result(res: common.SingleResult, top_domains=None, user_domain: str = "", cfg: dict | None = None,
+                      docs: bool = True):
+    """The saved model (models.saved.SavedModel) of a finished :func:`run_dns` day: its cuts, and
+    in the provenance the top-domain list's size and digest and the user domain its words were
+    made with."""
+    from ..models.saved import SavedModel, top_digest
+    n, dg = top_digest(top_domains)
+    prv = {"top_entries": n, "top_digest": dg, "user_domain": user_domain or ""}
+    prv.update(cfg or {})
+    return SavedModel.from_run(res.lda, res.stats["cuts"], "dns", prv, docs=docs)
+
+
+@traced("oni:dns.score")
+def score_dns(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
+              seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
+              top_domains=None, user_domain: str | None = None, feedback: dict | None = None, chunk_len: int = 0,
+              row_offset: int = 0, log=None, fuse: bool = True, prior_mass: float = 0.0) -> common.SingleResult:
+    """Score a batch of DNS responses against a saved model (``model``: models.saved.SavedModel of
+    source ``dns``) instead of training on it: words from the model's cuts, the given top-domain
+    list and the model's user domain (``user_domain`` None; another list or domain is allowed and
+    reported as ``model_top_mismatch``), then :func:`common.score_single_doc_events`.
+    ``prior_mass``: as :func:`oni355.pipeline.flow.score_flow`."""
+    if comm is not None and comm.dist:
+        raise NotImplementedError("fold-in scoring is single-GPU")
+    if model.source != "dns":
+        raise ValueError(f"a {model.source} model cannot score dns events")
+    if feedback and log:
+        log("analyst feedback is ignored when scoring against a saved model")
+    prior_mass = common.check_prior_mass(prior_mass, model)
+    mismatch = common.top_list_mismatch(model, top_domains, user_domain, log)
+    if user_domain is None:
+        user_domain = str(model.provenance.get("user_domain", ""))
+    timer = StageTimer(device)
+    with timer.stage("h2d"):
+        d = dict(device_cols) if device_cols is not None else to_device(cols, device)
+    with timer.stage("featurize"):
+        words, _, feats = featurize(d, None, top_set(top_domains), user_domain, cuts=model.cuts)
+    res = common.score_single_doc_events(common.u32_to_i64(d["ip_dst"]), words, model, tol, maxresults, sweeps,
+                                         avg_last, seed, chunk_len, row_offset, timer, fuse=fuse,
+                                         prior_mass=prior_mass)
+    res.stats["model_top_mismatch"] = mismatch
+    res.stats["cuts"] = {k: [int(x) for x in v] for k, v in model.cuts.items()}
     res.stats["features"] = feats
     return res

@@ -326,16 +326,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
                       lda=run)
 
 
-def model_word_ids(word_keys64: torch.Tensor, vocab: torch.Tensor) -> tuple[torch.Tensor, int]:
-    """(int32 id of every word key in the saved model's sorted ``vocab``, number of keys absent
-    from it): an absent word gets id V, the table's out-of-vocabulary row."""
-    V = int(vocab.numel())
-    if V == 0:
-        return torch.zeros_like(word_keys64, dtype=torch.int32), int(word_keys64.numel())
-    pos = torch.searchsorted(vocab, word_keys64).clamp_(max=V - 1)
-    hit = vocab[pos] == word_keys64
-    wids = torch.where(hit, pos, torch.full_like(pos, V)).to(torch.int32).contiguous()
-    return wids, int(word_keys64.numel() - int(hit.sum()))
+model_word_ids = common.model_word_ids
 
 
 @traced("oni:flow.score")
@@ -383,7 +374,7 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
         word_keys = ops.widen_pair(sw, dw)
         vocab = torch.from_numpy(model.vocab).to(dev)
         V = int(vocab.numel())
-        wids, n_oov = model_word_ids(word_keys, vocab)
+        wids, oov = model_word_ids(word_keys, vocab)
     with timer.stage("corpus"):
         K = int(model.K)
         G, KP = tiling_for(K, "dense")
@@ -434,7 +425,8 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
     parts = torch.stack([s1[ix[0]], s2[ix[0]]], 1).cpu()
     wparts = torch.stack([sw[ix[1]], dw[ix[1]]], 1).cpu()
     stats = corpus.stats()
-    stats.update({"n_flows": n, "loglik": None, "mode": "infer", "n_oov_tokens": n_oov,
+    # the miss counter of the vocabulary lookup is read here, with the result rows
+    stats.update({"n_flows": n, "loglik": None, "mode": "infer", "n_oov_tokens": int(oov.item()),
                   "foldin_launches": sum(fold.launches.values())})
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})

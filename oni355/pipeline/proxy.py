@@ -159,11 +159,9 @@ def featurize(cols: dict, device, comm: Comm | None, topset, allreduce_counts: b
     uo, uc = strcol("useragent")
     uh, _, _ = sops.string_features(uo, uc)
     if day is not None:
+        # min(count of the row's user agent in the table, 2^31 − 1), 0 for one absent from it
         tk, tc = day[1]
-        pos = torch.searchsorted(tk, uh).clamp_(max=max(tk.numel() - 1, 0))
-        hit = tk[pos] == uh if tk.numel() else torch.zeros_like(uh, dtype=torch.bool)
-        ua_freq = torch.where(hit, tc[pos] if tk.numel() else torch.zeros_like(uh), 0).clamp(max=2**31 - 1)
-        ua_freq = ua_freq.to(torch.int32).contiguous()
+        ua_freq, _ = ops.table_lookup(tk.contiguous(), uh.contiguous(), tc.contiguous())
         table = day[1]
     else:
         uq, inv, cnt = ua_histogram(uh)
@@ -243,4 +241,49 @@ def run_proxy(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxr
                                        timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag,
                                        key_bits=34)
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in cuts.items()}
+    res.stats["ua_table"] = ua_table
+    return res
+
+
+def model_from_result(res: common.SingleResult, top_domains=None, cfg: dict | None = None, docs: bool = True):
+    """The saved model (models.saved.SavedModel) of a finished :func:`run_proxy` day: its cuts, its
+    user-agent frequency table, and in the provenance the top-domain list's size and digest."""
+    from ..models.saved import SavedModel, top_digest
+    n, dg = top_digest(top_domains)
+    prv = {"top_entries": n, "top_digest": dg}
+    prv.update(cfg or {})
+    return SavedModel.from_run(res.lda, res.stats["cuts"], "proxy", prv, docs=docs, ua_table=res.stats["ua_table"])
+
+
+@traced("oni:proxy.score")
+def score_proxy(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
+                seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
+                top_domains=None, feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
+                fuse: bool = True, prior_mass: float = 0.0) -> common.SingleResult:
+    """Score a batch of proxy requests against a saved model (``model``: models.saved.SavedModel of
+    source ``proxy``) instead of training on it: words from the model's cuts and its user-agent
+    frequency table (a user agent the training day never saw counts 0) and the given top-domain
+    list (another list than the model's is allowed and reported as ``model_top_mismatch``), then
+    :func:`common.score_single_doc_events`. ``prior_mass``: as :func:`oni355.pipeline.flow.score_flow`."""
+    if comm is not None and comm.dist:
+        raise NotImplementedError("fold-in scoring is single-GPU")
+    if model.source != "proxy":
+        raise ValueError(f"a {model.source} model cannot score proxy events")
+    if feedback and log:
+        log("analyst feedback is ignored when scoring against a saved model")
+    prior_mass = common.check_prior_mass(prior_mass, model)
+    mismatch = common.top_list_mismatch(model, top_domains, None, log)
+    timer = StageTimer(device)
+    with timer.stage("h2d"):
+        d = dict(device_cols) if device_cols is not None else \
+            {k: staging.upload(a, device) for k, a in host_arrays(cols).items()}
+    with timer.stage("featurize"):
+        dev = d["clientip"].device
+        ua = (torch.from_numpy(model.ua_keys).to(dev), torch.from_numpy(model.ua_counts).to(dev))
+        words, _, _ = featurize(cols, device, None, top_set(top_domains), d=d, day=(model.cuts, ua))
+    res = common.score_single_doc_events(common.u32_to_i64(d["clientip"]), words, model, tol, maxresults, sweeps,
+                                         avg_last, seed, chunk_len, row_offset, timer, fuse=fuse,
+                                         prior_mass=prior_mass)
+    res.stats["model_top_mismatch"] = mismatch
+    res.stats["cuts"] = {k: [int(x) for x in v] for k, v in model.cuts.items()}
     return res
