@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -233,12 +234,33 @@ int oni_stager_stats(void* handle, int64_t* out2) {
   return 0;
 }
 
+// Whether this machine can pin memory a process already owns: 0 when hipHostRegister works on a
+// scratch host buffer, its hipError otherwise (virtualised GPUs refuse it with
+// hipErrorInvalidValue). A refused registration also stays behind as the thread's last error,
+// which the next launch check would report as its own, so it is cleared here.
+int oni_host_register_probe() {
+  constexpr size_t kProbeBytes = size_t(1) << 16;
+  void* p = std::aligned_alloc(4096, kProbeBytes);
+  if (p == nullptr) return (int)hipErrorOutOfMemory;
+  std::memset(p, 0, kProbeBytes);
+  hipError_t e = hipHostRegister(p, kProbeBytes, hipHostRegisterDefault);
+  if (e == hipSuccess) e = hipHostUnregister(p);
+  if (e != hipSuccess) (void)hipGetLastError();
+  std::free(p);
+  return (int)e;
+}
+
 // Zero-copy alternative to the ring: pin `src` in place (hipHostRegister), DMA it straight to
 // `dst` on `stream`, wait, unpin. Synchronous (the pages must stay pinned until the DMA is done).
+// Where the machine refuses the registration (oni_host_register_probe) the error is returned with
+// the thread's last error cleared; the caller stages through the ring's own pinned buffers instead.
 int oni_h2d_registered(const void* src, void* dst, int64_t bytes, hipStream_t stream) {
   if (bytes <= 0) return 0;
   hipError_t e = hipHostRegister(const_cast<void*>(src), (size_t)bytes, hipHostRegisterDefault);
-  if (e != hipSuccess) return (int)e;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return (int)e;
+  }
   e = hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   hipError_t u = hipHostUnregister(const_cast<void*>(src));

@@ -8,7 +8,8 @@ moves on to the next column (or the next decoded part) at once. The reference's 
 HDFS → Spark executors → lda-c corpus files shipped to MPI nodes.
 
 ``ONI_STAGED_H2D``: ``0`` plain ``tensor.to(device)`` (default), ``1`` ring, ``reg`` pin the
-source in place and DMA it directly. Measured on MI355X (``bench/h2d.py``, 550 MB of flow columns,
+source in place and DMA it directly (through the ring where the machine cannot register host
+memory, :func:`registered_supported`). Measured on MI355X (``bench/h2d.py``, 550 MB of flow columns,
 ``profiles/r1_h2d_staging.jsonl``): every path is PCIe-link bound, plain 9.98 ms (55.1 GB/s),
 registered 9.93 ms (55.4 GB/s), ring 10.63 ms (51.7 GB/s at 32 MB chunks x 16 threads; 27-31 GB/s
 at 4-8 MB chunks: the host memcpy into pinned memory is the ring's bottleneck). ROCm's own pageable
@@ -36,6 +37,7 @@ _lib.register("oni_stager_sync", [vp])
 _lib.register("oni_stager_stats", [vp, vp])
 _lib.register("oni_stager_destroy", [vp])
 _lib.register("oni_h2d_registered", [vp, vp, i64, vp])
+_lib.register("oni_host_register_probe", [])
 _lib.register("oni_h2d_pull", [vp, vp, i64, C.c_int, vp])
 _lib.register("oni_d2h_push", [vp, vp, i64, vp])
 
@@ -53,6 +55,7 @@ THREADS = int(os.environ.get("ONI_STAGE_THREADS", "16"))
 
 _lock = threading.Lock()
 _handle: C.c_void_p | None = None
+_reg_ok: bool | None = None
 
 
 def mode() -> str:
@@ -79,6 +82,21 @@ def _destroy() -> None:
             _handle = None
 
 
+def registered_supported() -> bool:
+    """Whether ``hipHostRegister`` can pin memory this process already owns (probed once, with a
+    device current). Virtualised GPUs refuse it; ``reg`` then stages through the ring, whose
+    buffers are allocated pinned, and says so once."""
+    global _reg_ok
+    with _lock:
+        if _reg_ok is None:
+            rc = _lib.lib().oni_host_register_probe()
+            _reg_ok = rc == 0
+            if not _reg_ok:
+                warnings.warn(f"ONI_STAGED_H2D=reg: hipHostRegister is not supported here (hipError {rc}); "
+                              "uploading through the pinned staging ring instead", RuntimeWarning, stacklevel=3)
+        return _reg_ok
+
+
 def upload_tensor(t: torch.Tensor, device) -> torch.Tensor:
     """Copy CPU tensor ``t`` to ``device`` (same dtype and shape) by the selected :func:`mode`."""
     device = torch.device(device)
@@ -90,7 +108,7 @@ def upload_tensor(t: torch.Tensor, device) -> torch.Tensor:
     nbytes = src.numel() * src.element_size()
     if nbytes:
         with torch.cuda.device(device):
-            if m == "reg":
+            if m == "reg" and registered_supported():
                 _lib.check(_lib.lib().oni_h2d_registered(src.data_ptr(), out.data_ptr(), nbytes, _lib.stream()),
                            "oni_h2d_registered")
             else:

@@ -30,7 +30,7 @@ def test_staged_upload_bitwise_many_sizes(gpu, monkeypatch, m):
     # kernels on the same stream are ordered after the queued copies
     s = float(tx.double().sum().item())
     assert s == pytest.approx(float(x.astype(np.float64).sum()), rel=1e-12)
-    if m == "1":
+    if m == "1" or not staging.registered_supported():  # "reg" rides the ring where it cannot pin in place
         assert staging.stats()["bytes"] - before["bytes"] == x.nbytes
     staging.sync()
 
