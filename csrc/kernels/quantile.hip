@@ -72,9 +72,15 @@ __global__ __launch_bounds__(256) void k_radix_hist(const uint32_t* __restrict__
   }
 }
 
-__global__ void k_f32_keys(const float* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
+// oni::f32_key on the values' bits, read as integers. Given a float, the compiler rewrites
+// u | 0x80000000 as -|x| and, in the unrolled grid-stride loop, as a packed f32 add of -0: an
+// arithmetic instruction, which quiets a signalling NaN. The key keeps every bit (spec.f32_key).
+__global__ void k_f32_keys(const uint32_t* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = oni::f32_key(x[i]);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t u = x[i];
+    out[i] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  }
 }
 
 __global__ void k_i64_keys(const int64_t* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
@@ -175,7 +181,7 @@ ONI_API int oni_radix_hist(const uint32_t* keys, int64_t n, int shift, int nbits
 }
 
 ONI_API int oni_f32_keys(const float* x, int64_t n, uint32_t* out, hipStream_t s) {
-  k_f32_keys<<<oni::grid_for(n), 256, 0, s>>>(x, n, out);
+  k_f32_keys<<<oni::grid_for(n), 256, 0, s>>>(reinterpret_cast<const uint32_t*>(x), n, out);
   return (int)hipGetLastError();
 }
 

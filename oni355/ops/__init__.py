@@ -22,7 +22,7 @@ from ..ref import spec
 from . import _lib
 
 __all__ = [
-    "f32_keys", "i64_keys", "quantile_cuts", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
+    "f32_keys", "i64_keys", "quantile_cuts", "radix_hist", "quantile_pick", "bin_keys", "flow_keys", "flow_wordify", "sell_fill",
     "sell_perm_z", "gibbs_pass", "foldin_pass", "prior_rows", "theta_rows_prior", "table_lookup", "gibbs_which", "GibbsKernel", "gibbs_apply", "mh_tables", "SAMPLER_MH", "CountMode", "copy_rows", "score", "select_below", "choose_tiling",
 ]
 
@@ -146,7 +146,7 @@ def quantile_cuts(keys: torch.Tensor, fracs, allreduce=None, n_global: int | Non
     L = _lib.lib() if dev else None
     knp = None if dev else _u32np(keys)
     ranks = spec.quantile_ranks(n, fracs).astype(np.int64)
-    prefix = np.zeros(len(fracs), dtype=np.uint64)
+    prefix = np.zeros(len(fracs), dtype=np.uint32)
     hist_buf = torch.zeros(16 << 11, dtype=torch.int32, device=keys.device) if dev else None
     for shift, nbits in _PASSES:
         top = shift + nbits
@@ -171,15 +171,8 @@ def quantile_cuts(keys: torch.Tensor, fracs, allreduce=None, n_global: int | Non
             h = spec.radix_hist(knp, shift, nbits, uniq.astype(np.uint32), mask)
             if allreduce is not None:
                 h = np.asarray(allreduce(h), dtype=np.int64).reshape(P, B)
-        cum = np.cumsum(h, axis=1)
-        for qi in range(len(fracs)):
-            c = cum[inv[qi]]
-            digit = int(np.searchsorted(c, ranks[qi], side="right"))
-            digit = min(digit, B - 1)
-            if digit > 0:
-                ranks[qi] -= c[digit - 1]
-            prefix[qi] |= np.uint64(digit << shift)
-    return prefix.astype(np.uint32)
+        prefix, ranks = spec.quantile_pick(h, inv * B, B, shift, prefix, ranks)
+    return prefix
 
 
 def quantile_cuts_multi(keys_list: list, fracs_list: list, allreduce=None, n_global: int | None = None) -> list:
@@ -200,7 +193,7 @@ def quantile_cuts_multi(keys_list: list, fracs_list: list, allreduce=None, n_glo
     dev = keys_list[0].device
     F = len(keys_list)
     ranks = [spec.quantile_ranks(n, f).astype(np.int64) for f in fracs_list]
-    prefix = [np.zeros(len(f), dtype=np.uint64) for f in fracs_list]
+    prefix = [np.zeros(len(f), dtype=np.uint32) for f in fracs_list]
     hist_buf = torch.zeros(F * (16 << 11), dtype=torch.int32, device=dev)
     dev_ar = allreduce is not None and getattr(allreduce, "accepts_tensors", False)
     for shift, nbits in _PASSES:
@@ -225,15 +218,9 @@ def quantile_cuts_multi(keys_list: list, fracs_list: list, allreduce=None, n_glo
             if allreduce is not None:
                 h_all = np.asarray(allreduce(h_all), dtype=np.int64)
         for f in range(F):
-            uniq, inv = uq[f]
-            cum = np.cumsum(h_all[offs[f]:offs[f + 1]].reshape(len(uniq), B), axis=1)
-            for qi in range(len(fracs_list[f])):
-                c = cum[inv[qi]]
-                digit = min(int(np.searchsorted(c, ranks[f][qi], side="right")), B - 1)
-                if digit > 0:
-                    ranks[f][qi] -= c[digit - 1]
-                prefix[f][qi] |= np.uint64(digit << shift)
-    return [p.astype(np.uint32) for p in prefix]
+            inv = uq[f][1]
+            prefix[f], ranks[f] = spec.quantile_pick(h_all, offs[f] + inv * B, B, shift, prefix[f], ranks[f])
+    return prefix
 
 
 def quantile_cuts_dev(keys_list: list, fracs_list: list, allreduce_=None, n_global: int | None = None) -> torch.Tensor:
@@ -283,6 +270,42 @@ def quantile_cuts_dev(keys_list: list, fracs_list: list, allreduce_=None, n_glob
         _lib.check(L.oni_quantile_pick(_lib.ptr(hist), _lib.ptr(bases[pi]), NQ, nbits, shift,
                                        _lib.ptr(prefix), _lib.ptr(rank), _lib.stream()), "oni_quantile_pick")
     return prefix
+
+
+def radix_hist(keys: torch.Tensor, shift: int, nbits: int, prefixes, mask: int) -> np.ndarray:
+    """One histogram pass of the radix select (k_radix_hist) on its own: for each of the P
+    ``prefixes`` (u32), the counts of digit ``(key >> shift) & (2^nbits - 1)`` over the keys with
+    ``key & mask == prefix``, as a (P, 2^nbits) int64 array. A duplicated prefix gets the full
+    count in every copy."""
+    _need(keys, torch.int32, "keys")
+    pre = np.asarray(prefixes, dtype=np.uint32).reshape(-1)
+    if not _is_dev(keys):
+        return spec.radix_hist(_u32np(keys), shift, nbits, pre, mask)
+    P, B = len(pre), 1 << nbits
+    hist = torch.zeros(P * B, dtype=torch.int32, device=keys.device)
+    _lib.check(_lib.lib().oni_radix_hist(_lib.ptr(keys), keys.numel(), shift, nbits,
+                                         _lib.ptr(_from_u32(pre, keys.device)), P, int(mask) & 0xFFFFFFFF,
+                                         _lib.ptr(hist), _lib.stream()), "oni_radix_hist")
+    return _u32np(hist).astype(np.int64).reshape(P, B)
+
+
+def quantile_pick(hist: torch.Tensor, base: torch.Tensor, nbits: int, shift: int, prefix: torch.Tensor,
+                  rank: torch.Tensor) -> None:
+    """The digit step of the radix select (k_quantile_pick), in place: query q reads the 2^nbits
+    counts (int32 holding u32 bits) at ``hist[base[q]:]``, ORs its digit into ``prefix[q]`` (int32
+    holding u32 bits) and narrows ``rank[q]`` (int64). See :func:`oni355.ref.spec.quantile_pick`."""
+    nq = prefix.numel()
+    _need(hist, torch.int32, "hist")
+    _need(base, torch.int32, "base", nq)
+    _need(prefix, torch.int32, "prefix")
+    _need(rank, torch.int64, "rank", nq)
+    if not _is_dev(hist):
+        p, r = spec.quantile_pick(_u32np(hist), base.numpy(), 1 << nbits, shift, _u32np(prefix), rank.numpy())
+        prefix.copy_(torch.from_numpy(p.view(np.int32)))
+        rank.copy_(torch.from_numpy(r))
+        return
+    _lib.check(_lib.lib().oni_quantile_pick(_lib.ptr(hist), _lib.ptr(base), nq, nbits, shift, _lib.ptr(prefix),
+                                            _lib.ptr(rank), _lib.stream()), "oni_quantile_pick")
 
 
 def bin_keys(keys: torch.Tensor, cuts: np.ndarray) -> torch.Tensor:

@@ -112,6 +112,19 @@ def string_features(offsets: torch.Tensor, chars: torch.Tensor):
     return outs
 
 
+def set_probe(hashes: torch.Tensor, hashset: ss.HashSet) -> torch.Tensor:
+    """uint8 membership flag per hash (int64 holding u64 bits) in ``hashset`` (k_set_probe): the
+    open-addressing probe the domain kernel runs on the top-domain and public-suffix tables."""
+    if hashes.dtype != torch.int64:
+        raise TypeError(f"hashes: expected torch.int64, got {hashes.dtype}")
+    if hashes.device.type != "cuda":
+        return torch.tensor([int(h) in hashset for h in _u64(hashes).tolist()], dtype=torch.uint8)
+    out = torch.empty(hashes.numel(), dtype=torch.uint8, device=hashes.device)
+    _lib.check(_lib.lib().oni_set_probe(_lib.ptr(hashes), hashes.numel(), _lib.ptr(_dev_topset(hashset, hashes.device)),
+                                        hashset.mask, _lib.ptr(out), _lib.stream()), "oni_set_probe")
+    return out
+
+
 def _split_cuts(flat: np.ndarray, sizes: list) -> list:
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     return [flat[off[i]:off[i + 1]] for i in range(len(sizes))]

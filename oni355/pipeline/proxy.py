@@ -35,8 +35,15 @@ RAW = [("method", 0xF, 23), ("ctype", 0xF, 16), ("respcode", 0x3FF, 0)]
 TOP_SHIFT = 31
 
 
+# The categorical rules are byte-wise ASCII rules (k_category_codes): str.strip() would also trim
+# U+001C-U+001F, U+0085 and U+00A0, str.upper() / str.lower() also fold non-ASCII letters.
+_ASCII_SPACE = " \t\n\r\v\f"
+_ASCII_UPPER = {c: c - 32 for c in range(ord("a"), ord("z") + 1)}
+_ASCII_LOWER = {c: c + 32 for c in range(ord("A"), ord("Z") + 1)}
+
+
 def ctype_class(s: str) -> int:
-    s = s.strip().lower()
+    s = s.strip(_ASCII_SPACE).translate(_ASCII_LOWER)
     best, blen = 10, -1
     for prefix, code in CTYPE_CLASSES:
         if (s == prefix if prefix in ("", "-") else s.startswith(prefix)) and len(prefix) > blen:
@@ -103,7 +110,7 @@ CTYPE_PATTERNS = tuple((p, 0 if p in ("", "-") else 1, c) for p, c in CTYPE_CLAS
 
 
 def method_code(s: str) -> int:
-    s = s.strip().upper()
+    s = s.strip(_ASCII_SPACE).translate(_ASCII_UPPER)
     return METHODS.index(s) if s in METHODS else 0
 
 

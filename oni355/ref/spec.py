@@ -148,6 +148,23 @@ def radix_hist(keys, shift: int, nbits: int, prefixes, mask: int) -> np.ndarray:
     return out
 
 
+def quantile_pick(hist, base, B: int, shift: int, prefix, rank):
+    """k_quantile_pick, and the host's digit step between radix passes: query q reads the B counts
+    at ``hist[base[q]:]`` and takes the first digit whose cumulative count exceeds its rank
+    (searchsorted(cumsum, rank, right), capped at B-1; rank -= cumsum[digit-1] when digit > 0;
+    prefix |= digit << shift). Returns the new (prefix u32, rank int64); the inputs are untouched."""
+    h = np.asarray(hist).reshape(-1).astype(np.int64)
+    prefix = np.array(prefix, dtype=U32)
+    rank = np.array(rank, dtype=np.int64)
+    for q, b in enumerate(np.asarray(base, dtype=np.int64).tolist()):
+        c = np.cumsum(h[b:b + B])
+        digit = min(int(np.searchsorted(c, rank[q], side="right")), B - 1)
+        if digit > 0:
+            rank[q] -= c[digit - 1]
+        prefix[q] |= U32(digit << shift)
+    return prefix, rank
+
+
 def bin_keys(keys, cuts):
     keys = np.asarray(keys, dtype=U32)
     cuts = np.asarray(cuts, dtype=U32)

@@ -150,6 +150,32 @@ def string_features(offsets, chars):
     return h, ln, en
 
 
+_SPACE = b" \t\n\r\v\f"
+
+
+def _fold(b: bytes, fold: int) -> bytes:
+    if fold == 1:
+        return bytes(c - 32 if 97 <= c <= 122 else c for c in b)
+    return _lower(b) if fold == 2 else b
+
+
+def category_codes(strings: list, patterns, fold: int, default: int) -> np.ndarray:
+    """k_category_codes, byte-wise: trim the six ASCII white-space bytes from both ends, fold
+    A-Z / a-z only (``fold`` 1 = upper, 2 = lower; the patterns are stored already folded), then the
+    code of the longest pattern ``(text, mode, code)`` that matches -- the whole string (mode 0)
+    or a prefix of it (mode 1); among patterns of equal length the first wins -- else ``default``."""
+    out = np.empty(len(strings), dtype=np.int32)
+    pats = [(p.encode() if isinstance(p, str) else bytes(p), m, c) for p, m, c in patterns]
+    for i, s in enumerate(strings):
+        s = _fold(bytes(s).strip(_SPACE), fold)
+        best, blen = default, -1
+        for p, mode, code in pats:
+            if len(p) > blen and (s == p if mode == 0 else s.startswith(p)):
+                best, blen = code, len(p)
+        out[i] = best
+    return out
+
+
 def pack_words(keys, cuts, kshift, raws, rmask, rshift, raw8=None, r8mask=0, r8shift=0) -> np.ndarray:
     n = len(keys[0]) if keys else len(raws[0])
     w = np.zeros(n, dtype=np.uint64)
