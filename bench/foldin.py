@@ -6,13 +6,15 @@
            launch)
   unfused  score_flow with sweep fusion off (one launch per sweep)
   prior    score_flow, fused, with the model's per-IP topic profiles as priors (--prior-mass)
+  fit      score_flow, fused, with fit=True: the per-IP and batch likelihood in a ``fit`` stage
 
   python bench/foldin.py --flows 12500000 --topics 20 --rounds 3 --out profiles/foldin/bench.json
 
 Prints one JSON line per day and a summary: median / min ms per day, ms per fold-in sweep (the
 ``foldin`` stage over the fold-in sweeps) and the run-to-run spread (max − min) of every variant.
 The model is saved with its document profiles; ``model_bytes`` is the size of that file with and
-without them. ``--variants`` picks the variants that alternate (default: all four).
+without them. ``--variants`` picks the variants that alternate (default: all five). The fit variant also reports
+its ``fit`` stage (device ms) and the batch's log-likelihood per token.
 """
 from __future__ import annotations
 
@@ -37,7 +39,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--prior-mass", type=float, default=5.0, help="the prior variant's mass")
-    ap.add_argument("--variants", default="train,infer,unfused,prior")
+    ap.add_argument("--variants", default="train,infer,unfused,prior,fit")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--source", choices=["flow", "dns", "proxy"], default="flow",
@@ -90,7 +92,8 @@ def main() -> int:
     variants = {"train": lambda: run_flow(day.cols, K=a.topics, sweeps=a.sweeps, **kw),
                 "infer": lambda: score_flow(day.cols, model, **ikw),
                 "unfused": lambda: score_flow(day.cols, model, fuse=False, **ikw),
-                "prior": lambda: score_flow(day.cols, model, prior_mass=a.prior_mass, **ikw)}
+                "prior": lambda: score_flow(day.cols, model, prior_mass=a.prior_mass, **ikw),
+                "fit": lambda: score_flow(day.cols, model, fit=True, **ikw)}
     variants = {n: variants[n] for n in a.variants.split(",")}
     for n, fn in variants.items():  # untimed warm-up of the fold-in variants
         if n != "train":
@@ -115,6 +118,12 @@ def main() -> int:
                 line["launches"] = res.stats["foldin_launches"]
                 if name == "prior":
                     line["n_prior_docs"] = res.stats["n_prior_docs"]
+                if name == "fit":
+                    line["fit_ms"] = round(t.get("fit_dev_s", t.get("fit_s", 0.0)) * 1e3, 4)
+                    line["fit_wall_ms"] = round(t.get("fit_s", 0.0) * 1e3, 4)  # host time of the stage
+                    line["score_ms"] = round(t.get("score_dev_s", t.get("score_s", 0.0)) * 1e3, 4)
+                    line["batch_loglik_per_token"] = res.stats["batch_loglik_per_token"]
+                    line["pairs"] = int(res.lda.c.pair_doc.numel())
                 line["overlap_with_training"] = round(len(top_train & set(res.rows.tolist())) / max(len(top_train), 1), 4)
             days[name].append(line)
             print(json.dumps(line), flush=True)
@@ -129,6 +138,10 @@ def main() -> int:
             vo = [x["vocab_ms"] for x in v]
             out.update({"vocab_ms_median": statistics.median(vo), "vocab_ms_min": min(vo),
                         "vocab_ms_spread": round(max(vo) - min(vo), 4)})
+        if all("fit_ms" in x for x in v):
+            fi = [x["fit_ms"] for x in v]
+            out.update({"fit_ms_median": statistics.median(fi), "fit_ms_min": min(fi),
+                        "fit_ms_spread": round(max(fi) - min(fi), 4)})
         return out
     summary = {n: summ(v) for n, v in days.items()}
     out = {"source": a.source, "flows": a.flows, "topics": a.topics, "train_sweeps": a.sweeps, "infer_sweeps": a.infer_sweeps,

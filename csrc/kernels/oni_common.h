@@ -85,4 +85,37 @@ __host__ __forceinline__ unsigned grid_for(int64_t n, int block = 256, int cap =
   return (unsigned)g;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The score dot θ_d·φ_w of every scoring kernel (k_score, k_pair_score, k_fit_pairs): f32, fixed k
+// order, 16-B row loads (rows are padded to KS, a multiple of 4), no fma contraction -- one
+// definition, so every kernel that scores a pair gives the same bits (ref.spec.dot_rows).
+// ---------------------------------------------------------------------------------------------
+template <int KS>
+__device__ __forceinline__ float dot_rows(const float* __restrict__ a, const float* __restrict__ b) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < KS; j += 4) {
+    const float4 x = *reinterpret_cast<const float4*>(a + j);
+    const float4 y = *reinterpret_cast<const float4*>(b + j);
+    s = s + x.x * y.x;
+    s = s + x.y * y.y;
+    s = s + x.z * y.z;
+    s = s + x.w * y.w;
+  }
+  return s;
+}
+
+__device__ __forceinline__ float dot_rows_dyn(const float* __restrict__ a, const float* __restrict__ b, int KS) {
+  float s = 0.f;
+  for (int j = 0; j < KS; j += 4) {
+    const float4 x = *reinterpret_cast<const float4*>(a + j);
+    const float4 y = *reinterpret_cast<const float4*>(b + j);
+    s = s + x.x * y.x;
+    s = s + x.y * y.y;
+    s = s + x.z * y.z;
+    s = s + x.w * y.w;
+  }
+  return s;
+}
+
 }  // namespace oni

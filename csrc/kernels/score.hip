@@ -13,33 +13,8 @@
 
 namespace {
 
-template <int KS>
-__device__ __forceinline__ float dot_rows(const float* __restrict__ a, const float* __restrict__ b) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < KS; j += 4) {
-    const float4 x = *reinterpret_cast<const float4*>(a + j);
-    const float4 y = *reinterpret_cast<const float4*>(b + j);
-    s = s + x.x * y.x;
-    s = s + x.y * y.y;
-    s = s + x.z * y.z;
-    s = s + x.w * y.w;
-  }
-  return s;
-}
-
-__device__ __forceinline__ float dot_rows_dyn(const float* __restrict__ a, const float* __restrict__ b, int KS) {
-  float s = 0.f;
-  for (int j = 0; j < KS; j += 4) {
-    const float4 x = *reinterpret_cast<const float4*>(a + j);
-    const float4 y = *reinterpret_cast<const float4*>(b + j);
-    s = s + x.x * y.x;
-    s = s + x.y * y.y;
-    s = s + x.z * y.z;
-    s = s + x.w * y.w;
-  }
-  return s;
-}
+using oni::dot_rows;
+using oni::dot_rows_dyn;
 
 template <int KS>
 __global__ __launch_bounds__(256) void k_score(const float* __restrict__ theta, const float* __restrict__ phi,

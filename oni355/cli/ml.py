@@ -60,6 +60,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="score the day's events against this saved model (fold-in inference) instead of training")
     ap.add_argument("--infer-sweeps", type=int, default=30, help="--model: fold-in sweeps")
     ap.add_argument("--infer-avg-last", type=int, default=10, help="--model: sweeps averaged into theta")
+    ap.add_argument("--infer-fit", action="store_true",
+                    help="--model: also report how well the model fits the batch: the batch log-likelihood and "
+                         "perplexity in metrics.jsonl, and <source>_fit.csv with the MAXRESULTS worst-fitting IPs")
     ap.add_argument("--infer-prior-mass", type=float, default=0.0, metavar="M",
                     help="--model: fold an IP the model knows in under its training-day topic profile, weighted "
                          "by at most M pseudo-tokens (0: off, every IP starts from the flat prior)")
@@ -250,6 +253,8 @@ def main(argv=None) -> int:
         opt = "--model" if a.model else "--save-model"
         if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
+    if a.infer_fit and not a.model:
+        raise SystemExit("oni-ml: --infer-fit reports the fit of a saved model; it needs --model FILE")
     if a.model:
         for flag, val in (("--ckpt-dir", a.ckpt_dir), ("--ldac-out", a.ldac_out), ("--save-model", a.save_model)):
             if val:
@@ -331,7 +336,7 @@ def main(argv=None) -> int:
                              "without: save the model again with --save-model and no --no-model-docs")
         score_kw = dict(tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps, avg_last=a.infer_avg_last,
                         seed=cfg.SEED, device=device, comm=comm, feedback=fb, chunk_len=cfg.CHUNK_LEN,
-                        row_offset=row_off, log=log, prior_mass=a.infer_prior_mass)
+                        row_offset=row_off, log=log, prior_mass=a.infer_prior_mass, fit=a.infer_fit)
         if a.source == "flow":
             from ..pipeline.flow import score_flow
             res = score_flow(cols, model, **score_kw)
@@ -379,6 +384,11 @@ def main(argv=None) -> int:
                  "device": device, "load_s": t_load, **{k: v for k, v in res.timings.items()},
                  **{k: v for k, v in res.stats.items() if isinstance(v, (int, float, str)) or v is None}})
         log(f"wrote {len(rendered)} rows -> {out}")
+        if a.infer_fit:
+            fp = rio.write_csv(rio.fit_path(cfg.LPATH, a.source, a.date), rio.FIT_COLUMNS,
+                               rio.fit_rows(a.source, cols, res.fit, cfg.MAXRESULTS))
+            log(f"batch fit: loglik/token {res.stats['batch_loglik_per_token']}, perplexity "
+                f"{res.stats['batch_perplexity']} -> {fp}")
     if a.ldac_out:
         from ..io import ldac
         d = os.path.join(a.ldac_out, f"rank{rank}") if world > 1 else a.ldac_out

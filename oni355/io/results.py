@@ -397,6 +397,48 @@ def read_csv(path: str) -> tuple[list[str], list[list[str]]]:
         return header, [row for row in r]
 
 
+FIT_COLUMNS = ["ip", "tokens", "oov_tokens", "loglik", "loglik_per_token", "min_score"]
+
+
+def _doc_addresses(source: str, cols: dict, keys: np.ndarray) -> list[str]:
+    """Document keys as the results writer prints addresses: dotted IPv4, and for a flow day with
+    IPv6 columns the text of the day-dictionary keys (``sip6`` / ``dip6``, see with_ipv6_keys)."""
+    out = [ip_str(k) for k in keys]
+    if source == "flow" and any(k in cols for k in ("sip6", "dip6")):
+        from ..pipeline.flow import V6_KEY_BASE, with_ipv6_keys
+        keyed = with_ipv6_keys(cols, None)
+        idx = np.nonzero(keys >= V6_KEY_BASE)[0]
+        for k4, k6 in (("sip", "sip6"), ("dip", "dip6")):
+            if k6 not in keyed or not idx.size:
+                continue
+            uk, first = np.unique(np.asarray(keyed[k4]).astype(np.int64), return_index=True)
+            pos = np.minimum(np.searchsorted(uk, keys[idx]), uk.size - 1)
+            ok = uk[pos] == keys[idx]
+            for i, t in zip(idx[ok], keyed[k6].take(first[pos[ok]]).to_list()):
+                if t:
+                    out[i] = t
+    return out
+
+
+def fit_rows(source: str, cols: dict, fit, maxresults: int) -> list[list]:
+    """Rows of ``<source>_fit.csv``: the ``maxresults`` documents with the lowest log-likelihood per
+    token among those with at least one token, ties by document key (``fit``: common.BatchFit)."""
+    keys = fit.doc_keys.cpu().numpy()
+    ll, tok = fit.loglik.cpu().numpy(), fit.tokens.cpu().numpy()
+    oov, mn = fit.oov_tokens.cpu().numpy(), fit.min_score.cpu().numpy()
+    sel = np.nonzero(tok > 0)[0]
+    per = ll[sel] / tok[sel]
+    o = np.lexsort((keys[sel], per))[:max(int(maxresults), 0)]
+    sel, per = sel[o], per[o]
+    ips = _doc_addresses(source, cols, keys[sel])
+    return [[ip, int(tok[d]), int(oov[d]), repr(float(ll[d])), repr(float(p)), repr(float(mn[d]))]
+            for ip, d, p in zip(ips, sel, per)]
+
+
+def fit_path(lpath: str, source: str, date: str) -> str:
+    return os.path.join(lpath, source, date, f"{source}_fit.csv")
+
+
 def results_path(lpath: str, source: str, date: str) -> str:
     return os.path.join(lpath, source, date, f"{source}_results.csv")
 

@@ -1176,6 +1176,60 @@ def table_lookup(keys: torch.Tensor, queries: torch.Tensor, values: torch.Tensor
     return out, misses
 
 
+class DocFit(NamedTuple):
+    """What :func:`doc_fit` returns: per-document arrays [D] and the totals."""
+    ll: torch.Tensor          # f64 Σ count · log(score)
+    tokens: torch.Tensor      # i64 Σ count
+    oov_tokens: torch.Tensor  # i64 Σ count over the out-of-vocabulary row
+    min_score: torch.Tensor   # f32 smallest pair score, +inf without pairs
+    tot: torch.Tensor         # f64 [4]: Σ ll, Σ tokens, Σ oov tokens, documents with a token
+
+
+def doc_fit(theta: torch.Tensor, table: torch.Tensor, pair_doc: torch.Tensor, pair_word: torch.Tensor,
+            pair_count: torch.Tensor, D: int, oov_id: int, grid: int | None = None) -> DocFit:
+    """Per-document log-likelihood of a batch under a model table (k_fit_pairs / k_fit_docs /
+    k_fit_total): ll_d = Σ_pairs count · log(θ_d·φ_w) in f64 over the doc-major distinct pairs, with
+    each document's tokens, out-of-vocabulary tokens (``pair_word == oov_id``) and smallest pair
+    score, and their totals. ``theta`` f32 [D, KS], ``table`` f32 [oov_id + 1, KS], the pair arrays
+    int32 [P] with ``pair_doc`` non-decreasing. The pair score is bitwise :func:`pair_score`'s; a
+    score of 0 gives -inf for its document and the total. Same inputs, same bits, whatever ``grid``
+    (blocks per pass; default sized from P and D). CPU tensors run the oracle
+    (:func:`oni355.ref.fit_spec.doc_fit`)."""
+    from ..ref import fit_spec
+    D, oov_id, P = int(D), int(oov_id), int(pair_doc.numel())
+    if theta.dim() != 2 or table.dim() != 2 or theta.shape[1] != table.shape[1] or theta.shape[1] % 4:
+        raise ValueError("doc_fit: theta [D, KS] and table [V + 1, KS] with one KS, a multiple of 4")
+    KS = int(theta.shape[1])
+    if D < 0 or D > theta.shape[0] or oov_id < 0 or oov_id >= table.shape[0]:
+        raise ValueError("doc_fit: D rows of theta and row oov_id of table must exist")
+    _need(theta, torch.float32, "theta")
+    _need(table, torch.float32, "table")
+    for t, nm in ((pair_doc, "pair_doc"), (pair_word, "pair_word"), (pair_count, "pair_count")):
+        _need(t, torch.int32, nm, P)
+        if t.device != theta.device:
+            raise ValueError("doc_fit: the pairs must be on theta's device")
+    if table.device != theta.device:
+        raise ValueError("doc_fit: table must be on theta's device")
+    if grid is not None and not 1 <= int(grid) <= 65535:
+        raise ValueError("doc_fit: grid must be in [1, 65535]")
+    if not _is_dev(theta):
+        return DocFit(*(torch.from_numpy(x) for x in fit_spec.doc_fit(
+            theta.numpy(), table.numpy(), pair_doc.numpy(), pair_word.numpy(), pair_count.numpy(), D, oov_id)))
+    dev = theta.device
+    ll = torch.empty(D, dtype=torch.float64, device=dev)
+    tok = torch.empty(D, dtype=torch.int64, device=dev)
+    oov = torch.empty(D, dtype=torch.int64, device=dev)
+    mn = torch.empty(D, dtype=torch.float32, device=dev)
+    tot = torch.empty(4, dtype=torch.float64, device=dev)
+    # 7 words per wave of 64 pairs (head and tail partial), 4 per tile of 256 documents: never initialised
+    scratch = torch.empty(max(7 * ((P + 63) // 64) + 4 * ((D + 255) // 256), 1), dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().oni_doc_fit(_lib.ptr(theta), _lib.ptr(table), KS, _lib.ptr(pair_doc), _lib.ptr(pair_word),
+                                      _lib.ptr(pair_count), P, D, oov_id, _lib.ptr(ll), _lib.ptr(tok), _lib.ptr(oov),
+                                      _lib.ptr(mn), _lib.ptr(tot), _lib.ptr(scratch), int(grid or 0), _lib.stream()),
+               "oni_doc_fit")
+    return DocFit(ll, tok, oov, mn, tot)
+
+
 def phi_rows(nw: torch.Tensor, nk: torch.Tensor, K: int, add: float, vb: float) -> torch.Tensor:
     """φ = (n_wk + add) / (n_k + vb) in f32 (k_phi_rows), zero past K; int32 or int64 counts."""
     V, KS = nw.shape

@@ -992,6 +992,48 @@ def top_n(score: torch.Tensor, tol: float, maxresults: int, comm: Comm | None, r
 
 
 @dataclass
+class BatchFit:
+    """How well the model fits the scored batch (``score_*(fit=True)``): the plug-in log-likelihood
+    of every document under its fold-in θ and the model's table (:func:`oni355.ops.doc_fit`).
+    Tensors on the run's device, document order = ``doc_keys`` (the batch's sorted document keys)."""
+    doc_keys: torch.Tensor    # int64 [D]
+    loglik: torch.Tensor      # f64 [D] Σ count · log(θ_d·φ_w); -inf where a pair scores exactly 0
+    tokens: torch.Tensor      # int64 [D]
+    oov_tokens: torch.Tensor  # int64 [D]
+    min_score: torch.Tensor   # f32 [D] smallest pair score (+inf for a document without tokens)
+    totals: torch.Tensor      # f64 [4]: Σ loglik, Σ tokens, Σ oov_tokens, documents with a token
+
+    def stats(self) -> dict:
+        """The batch keys of ``stats`` / the metrics line (one small read from the device)."""
+        ll, tok, oov, _ = self.totals.cpu().tolist()
+        per = ll / tok if tok > 0 else None
+        with np.errstate(over="ignore"):
+            ppl = float(np.exp(np.float64(-per))) if per is not None else None
+        return {"batch_loglik": ll, "batch_tokens": int(tok), "batch_oov_tokens": int(oov),
+                "batch_loglik_per_token": per, "batch_perplexity": ppl}
+
+
+@traced("oni:batch_fit")
+def batch_fit(theta: torch.Tensor, table: torch.Tensor, pairs, D: int, V: int, ids: torch.Tensor | None = None,
+              doc_keys: torch.Tensor | None = None) -> BatchFit:
+    """Per-document and batch likelihood after fold-in. ``pairs``: the corpus PairSet of the batch
+    (doc-major whatever order the score plan keeps its pairs in), or None on the CPU path, where
+    the (doc, word, count) pairs come from ``ids`` = doc·(V + 1) + word id of every token, the ids
+    that path's score plan is built from. Word id V is the out-of-vocabulary row of ``table``.
+    Nothing here waits for the device."""
+    if pairs is not None:
+        pd, pw, pc = pairs.pair_doc, pairs.pair_word, pairs.pair_cnt
+    else:
+        uniq, cnt = torch.unique(ids, return_counts=True)
+        pd, pw, pc = ((uniq // (V + 1)).to(torch.int32).contiguous(), (uniq % (V + 1)).to(torch.int32).contiguous(),
+                      cnt.to(torch.int32).contiguous())
+    f = ops.doc_fit(theta, table, pd, pw, pc, D, V)
+    if doc_keys is None:
+        doc_keys = torch.arange(D, dtype=torch.int64, device=theta.device)
+    return BatchFit(doc_keys, f.ll, f.tokens, f.oov_tokens, f.min_score, f.tot)
+
+
+@dataclass
 class SingleResult:
     rows: np.ndarray      # global row ids, ascending score
     scores: np.ndarray
@@ -999,6 +1041,7 @@ class SingleResult:
     timings: dict
     stats: dict
     lda: object = None
+    fit: BatchFit | None = None  # score_dns / score_proxy with fit=True
 
 
 def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K: int, sweeps: int, tol: float,
@@ -1092,12 +1135,14 @@ def top_list_mismatch(model, top_domains, user_domain: str | None, log=None) -> 
 @traced("oni:score_single_doc_events")
 def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, model, tol: float, maxresults: int,
                             sweeps: int, avg_last: int, seed: int, chunk_len: int, row_offset: int,
-                            timer: StageTimer, fuse: bool = True, prior_mass: float = 0.0) -> SingleResult:
+                            timer: StageTimer, fuse: bool = True, prior_mass: float = 0.0,
+                            fit: bool = False) -> SingleResult:
     """The DNS / proxy half of scoring against a saved model, after wordification: one (doc, word)
     token per event. Word ids through the model's vocabulary (an unseen word → id V, the
     out-of-vocabulary row), the batch's own documents folded in against the frozen table
     (models.foldin.FoldIn, optionally under per-IP priors), θ, then the one-sided score plan and
-    top-N against the model's table -- :func:`oni355.pipeline.flow.score_flow` for one endpoint."""
+    top-N against the model's table -- :func:`oni355.pipeline.flow.score_flow` for one endpoint.
+    ``fit``: also the batch's likelihood under the model (:func:`batch_fit`), in a ``fit`` stage."""
     from ..models.foldin import FoldIn
     from ..models.gibbs import tiling_for
     from ..ref.foldin_spec import V6_KEY_BASE
@@ -1133,6 +1178,7 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
         fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
         fold.run(sweeps, avg_last)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
+    ids = None
     with timer.stage("score_prep"):
         theta = fold.theta()
         if pairs is not None and not SCORE_TILES:
@@ -1140,12 +1186,17 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
         else:
             # the torch reference plan over (doc row, word id) pairs (score_plan looks word KEYS up
             # in the vocabulary, which unseen words are not in)
-            uniq, pinv = torch.unique(inv.to(torch.int64) * (V + 1) + wids.to(torch.int64), return_inverse=True)
+            ids = inv.to(torch.int64) * (V + 1) + wids.to(torch.int64)
+            uniq, pinv = torch.unique(ids, return_inverse=True)
             plan = ScorePlan((uniq // (V + 1)).to(torch.int32).contiguous(),
                              (uniq % (V + 1)).to(torch.int32).contiguous(), [pinv.to(torch.int32).contiguous()])
     with timer.stage("score"):
         score, _, _ = plan_score(theta, table, plan, tol, hist=hist)
         rows, scs = top_n(score, tol, maxresults, None, row_offset, hist=hist, order=plan.order)
+    bfit = None
+    if fit:
+        with timer.stage("fit"):
+            bfit = batch_fit(theta, table, pairs, D, V, ids=ids, doc_keys=udoc)
     t = timer.summary()
     t["records_scored"] = n
     t["sweeps"] = int(sweeps)
@@ -1156,9 +1207,11 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
                   "foldin_launches": sum(fold.launches.values())})
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
+    if bfit is not None:
+        stats.update(bfit.stats())
     stats.update({f"model_{k}": v for k, v in model.provenance.items() if isinstance(v, (int, float, str, bool))})
     return SingleResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), words=words.numpy().view(np.uint64),
-                        timings=t, stats=stats, lda=fold)
+                        timings=t, stats=stats, lda=fold, fit=bfit)
 
 
 def rows_in_order(gid_all: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:

@@ -205,6 +205,7 @@ class FlowResult:
     timings: dict = field(default_factory=dict)
     stats: dict = field(default_factory=dict)
     lda: object = None
+    fit: object = None         # common.BatchFit of score_flow(fit=True)
 
 
 def feedback_tokens(fb_cols: dict | None, cuts: FlowCuts, device, dupfactor: int):
@@ -333,7 +334,7 @@ model_word_ids = common.model_word_ids
 def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
                seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
                feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
-               fuse: bool = True, prior_mass: float = 0.0) -> FlowResult:
+               fuse: bool = True, prior_mass: float = 0.0, fit: bool = False) -> FlowResult:
     """Score a batch of flows against a saved model (``model``: models.saved.SavedModel) instead of
     training on it: words from the model's cuts, ids through its vocabulary (unseen words → the
     out-of-vocabulary row), the batch's own IP documents folded in against the frozen φ
@@ -341,7 +342,11 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
 
     ``prior_mass`` > 0: an IP the model has a document profile of is folded in under the Dirichlet
     prior α + min(its training tokens, prior_mass)·θ_train (ops.prior_rows) instead of the flat α, in
-    the draws and in θ; an IP the model does not know, and every IP at 0, behaves as without."""
+    the draws and in θ; an IP the model does not know, and every IP at 0, behaves as without.
+
+    ``fit``: after scoring, a timed ``fit`` stage computes every IP's log-likelihood under the model
+    and its fold-in θ and the batch totals (:func:`common.batch_fit`): ``FlowResult.fit`` and the
+    ``batch_*`` stats. Off, nothing of it runs."""
     from ..models.corpus import auto_chunk_len, build_corpus
     from ..models.foldin import FoldIn
     from ..models.gibbs import tiling_for
@@ -401,6 +406,7 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
         fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
         fold.run(sweeps, avg_last)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
+    ids = None
     with timer.stage("score_prep"):
         theta = fold.theta()
         if pairs is not None and not common.SCORE_TILES:
@@ -417,6 +423,10 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
         score, s1, s2 = common.plan_score(theta, table, plan, tol, hist=hist, want_parts=True)
         rows, scs, rpos = common.top_n(score, tol, maxresults, None, row_offset, hist=hist, order=plan.order,
                                        return_pos=True)
+    bfit = None
+    if fit:
+        with timer.stage("fit"):
+            bfit = common.batch_fit(theta, table, pairs, D, V, ids=ids, doc_keys=udoc)
     t = timer.summary()
     t["records_scored"] = n
     t["sweeps"] = int(sweeps)
@@ -430,7 +440,10 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
                   "foldin_launches": sum(fold.launches.values())})
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
+    if bfit is not None:
+        stats.update(bfit.stats())
     stats.update({f"model_{k}": v for k, v in model.provenance.items() if isinstance(v, (int, float, str, bool))})
     return FlowResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), src_scores=parts[:, 0].numpy(),
                       dst_scores=parts[:, 1].numpy(), src_words=wparts[:, 0].numpy().view(np.uint32),
-                      dst_words=wparts[:, 1].numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats, lda=fold)
+                      dst_words=wparts[:, 1].numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats, lda=fold,
+                      fit=bfit)

@@ -48,6 +48,9 @@ HIP_FLAGS = [
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
     "-I", os.path.join(CSRC, "kernels"),
 ]
+# per-file additions: fit.hip adds f32 pairs lane-wise all over (the scan, the butterflies); it is
+# built without the packed-f32 VALU forms so that every such add is the plain scalar instruction
+HIP_FILE_FLAGS = {"fit.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 CXX_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-fopenmp", "-Wall", "-Wno-unused-function",
              "-I", os.path.join(CSRC, "native")]
 
@@ -118,6 +121,7 @@ def build_hip(n_jobs: int, verbose: bool) -> str:
         o = os.path.join(OBJ, "hip", os.path.basename(s) + ".o")
         objs.append(o)
         extra = [f'-DONI_SRC_HASH="{src_hash}"'] if os.path.basename(s) == "build_info.hip" else []
+        extra += HIP_FILE_FLAGS.get(os.path.basename(s), [])
         cmd = [HIPCC, *HIP_FLAGS, *extra, "-c", s, "-o", o]
         key = _obj_key(s, cmd, hdr)
         if _stale(o, key):
