@@ -7,6 +7,8 @@
   unfused  score_flow with sweep fusion off (one launch per sweep)
   prior    score_flow, fused, with the model's per-IP topic profiles as priors (--prior-mass)
   fit      score_flow, fused, with fit=True: the per-IP and batch likelihood in a ``fit`` stage
+  vb       score_flow with method="vb": the variational fold-in (--infer-iters iterations, one
+           launch, no seed); only runs when named in --variants
 
   python bench/foldin.py --flows 12500000 --topics 20 --rounds 3 --out profiles/foldin/bench.json
 
@@ -36,6 +38,7 @@ def main() -> int:
     ap.add_argument("--sweeps", type=int, default=200, help="training sweeps")
     ap.add_argument("--infer-sweeps", type=int, default=30)
     ap.add_argument("--avg-last", type=int, default=10)
+    ap.add_argument("--infer-iters", type=int, default=20, help="the vb variant's iterations")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--prior-mass", type=float, default=5.0, help="the prior variant's mass")
@@ -93,7 +96,8 @@ def main() -> int:
                 "infer": lambda: score_flow(day.cols, model, **ikw),
                 "unfused": lambda: score_flow(day.cols, model, fuse=False, **ikw),
                 "prior": lambda: score_flow(day.cols, model, prior_mass=a.prior_mass, **ikw),
-                "fit": lambda: score_flow(day.cols, model, fit=True, **ikw)}
+                "fit": lambda: score_flow(day.cols, model, fit=True, **ikw),
+                "vb": lambda: score_flow(day.cols, model, method="vb", iters=a.infer_iters, **ikw)}
     variants = {n: variants[n] for n in a.variants.split(",")}
     for n, fn in variants.items():  # untimed warm-up of the fold-in variants
         if n != "train":
@@ -116,6 +120,9 @@ def main() -> int:
                 line["vocab_ms"] = round(t.get("vocab_dev_s", t.get("vocab_s", 0.0)) * 1e3, 4)
                 line["vocab_wall_ms"] = round(t.get("vocab_s", 0.0) * 1e3, 4)  # host time of the stage
                 line["launches"] = res.stats["foldin_launches"]
+                if name == "vb":
+                    line["foldin_ms"] = round(t.get("foldin_dev_s", t.get("foldin_s", 0.0)) * 1e3, 4)
+                    line["infer_iters"] = res.stats["infer_iters"]
                 if name == "prior":
                     line["n_prior_docs"] = res.stats["n_prior_docs"]
                 if name == "fit":

@@ -60,6 +60,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="score the day's events against this saved model (fold-in inference) instead of training")
     ap.add_argument("--infer-sweeps", type=int, default=30, help="--model: fold-in sweeps")
     ap.add_argument("--infer-avg-last", type=int, default=10, help="--model: sweeps averaged into theta")
+    ap.add_argument("--infer-method", choices=["gibbs", "vb"], default=None,
+                    help="--model: how an IP's topic mix is estimated: gibbs (default, the sampled fold-in chain) "
+                         "or vb (deterministic variational fold-in: no seed, --infer-sweeps/--infer-avg-last unused)")
+    ap.add_argument("--infer-iters", type=int, default=None, metavar="N",
+                    help="--model --infer-method vb: fixed-point iterations (default 20, lda-c's var max iter)")
     ap.add_argument("--infer-fit", action="store_true",
                     help="--model: also report how well the model fits the batch: the batch log-likelihood and "
                          "perplexity in metrics.jsonl, and <source>_fit.csv with the MAXRESULTS worst-fitting IPs")
@@ -255,7 +260,12 @@ def main(argv=None) -> int:
             raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
     if a.infer_fit and not a.model:
         raise SystemExit("oni-ml: --infer-fit reports the fit of a saved model; it needs --model FILE")
+    for flag, val in (("--infer-method", a.infer_method), ("--infer-iters", a.infer_iters)):
+        if val is not None and not a.model:
+            raise SystemExit(f"oni-ml: {flag} chooses how a saved model's day is folded in; it needs --model FILE")
     if a.model:
+        if a.infer_iters is not None and a.infer_iters < 0:
+            raise SystemExit("oni-ml: --infer-iters must be ≥ 0")
         for flag, val in (("--ckpt-dir", a.ckpt_dir), ("--ldac-out", a.ldac_out), ("--save-model", a.save_model)):
             if val:
                 raise SystemExit(f"oni-ml: --model scores against a saved model and trains nothing; {flag} does not apply")
@@ -336,7 +346,8 @@ def main(argv=None) -> int:
                              "without: save the model again with --save-model and no --no-model-docs")
         score_kw = dict(tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps, avg_last=a.infer_avg_last,
                         seed=cfg.SEED, device=device, comm=comm, feedback=fb, chunk_len=cfg.CHUNK_LEN,
-                        row_offset=row_off, log=log, prior_mass=a.infer_prior_mass, fit=a.infer_fit)
+                        row_offset=row_off, log=log, prior_mass=a.infer_prior_mass, fit=a.infer_fit,
+                        method=a.infer_method or "gibbs", iters=20 if a.infer_iters is None else a.infer_iters)
         if a.source == "flow":
             from ..pipeline.flow import score_flow
             res = score_flow(cols, model, **score_kw)

@@ -117,3 +117,50 @@ class FoldIn:
 
     def phi(self) -> torch.Tensor:
         return self.table
+
+
+class VarFoldIn:
+    """Variational (mean-field) fold-in over ``corpus``' distinct (doc, word) pairs: the
+    deterministic, seed-free counterpart of :class:`FoldIn` (ops.vfold, one launch for every
+    iteration of every document). Same inputs as FoldIn without ``seed`` / ``fuse``; it holds no
+    topic assignments and no count rows."""
+
+    def __init__(self, corpus: Corpus, table: torch.Tensor, K: int, alpha: float, prior: torch.Tensor | None = None):
+        c = corpus
+        if table.dim() != 2 or table.dtype != torch.float32 or table.shape[0] != c.V:
+            raise ValueError(f"the word table must be f32 [{c.V}, KS] (one row per corpus word id)")
+        if table.shape[1] % 4 or table.shape[1] < K:
+            raise ValueError("the table's row width must be a multiple of 4, at least K")
+        if table.device != c.pair_word.device:
+            raise ValueError("corpus and word table live on different devices")
+        if c.split is not None:
+            raise NotImplementedError("fold-in scoring is single-GPU")
+        self.c, self.table = c, table.contiguous()
+        self.K, self.alpha, self.KS = int(K), float(alpha), int(table.shape[1])
+        self.device = table.device
+        if prior is not None:
+            if prior.dtype != torch.float32 or tuple(prior.shape) != (max(c.D, 1), self.KS) or prior.device != self.device:
+                raise ValueError(f"the prior must be f32 [{max(c.D, 1)}, {self.KS}] on the corpus' device")
+            prior = prior[:c.D].contiguous()
+        self.prior = prior
+        self._theta = None
+        self.iters_done = 0
+        self.launches = {"vfold": 0}
+
+    @traced("oni:vfold.run")
+    def run(self, iters: int = 20) -> "VarFoldIn":
+        c = self.c
+        self._theta = ops.vfold(c.pair_word.contiguous(), c.pair_cnt.contiguous(), c.doc_pair_ptr.contiguous(),
+                                self.table, self.K, self.alpha, self.prior, iters)
+        self.launches = {"vfold": 1}
+        self.iters_done = int(iters)
+        return self
+
+    def theta(self) -> torch.Tensor:
+        """θ f32 [D, KS], zero past K."""
+        if self._theta is None:
+            raise RuntimeError("VarFoldIn.theta() before run()")
+        return self._theta
+
+    def phi(self) -> torch.Tensor:
+        return self.table

@@ -1239,3 +1239,44 @@ def phi_rows(nw: torch.Tensor, nk: torch.Tensor, K: int, add: float, vb: float) 
                                        _lib.stream()),
                "oni_phi_rows")
     return out
+
+
+def vfold(pair_word: torch.Tensor, pair_cnt: torch.Tensor, doc_pair_ptr: torch.Tensor, table: torch.Tensor, K: int,
+          alpha: float, prior: torch.Tensor | None = None, iters: int = 20, want_gamma: bool = False):
+    """Variational fold-in (k_vfold): mean-field θ of D documents against the frozen ``table``, every
+    iteration of every document in one launch, deterministic and seed-free
+    (:func:`oni355.ref.vfold_spec.vfold` is the specification). ``pair_word`` / ``pair_cnt`` int32 [P]
+    doc-major with every word id below the table's row count, ``doc_pair_ptr`` int64 [D + 1],
+    ``table`` f32 [rows, KS] (KS a multiple of 4, at most 256, columns ≥ K zero), ``prior`` f32
+    [D, KS] rows in α's place or None. Returns θ f32 [D, KS] (zero past K), with ``want_gamma``
+    (θ, γ). CPU tensors run the specification in float64, rounded to f32."""
+    from ..ref import vfold_spec
+    P, D, K, iters = int(pair_word.numel()), int(doc_pair_ptr.numel()) - 1, int(K), int(iters)
+    _need(pair_word, torch.int32, "pair_word")
+    _need(pair_cnt, torch.int32, "pair_cnt", P)
+    _need(doc_pair_ptr, torch.int64, "doc_pair_ptr")
+    _need(table, torch.float32, "table")
+    if D < 0 or table.dim() != 2 or table.shape[1] % 4 or table.shape[1] > 256:
+        raise ValueError("vfold: doc_pair_ptr int64 [D + 1] and table f32 [rows, KS], KS a multiple of 4 up to 256")
+    KS = int(table.shape[1])
+    if not 1 <= K <= KS or iters < 0:
+        raise ValueError("vfold: 1 ≤ K ≤ KS and iters ≥ 0")
+    if prior is None and not alpha > 0:
+        raise ValueError("vfold: alpha must be > 0")
+    dev = table.device
+    if prior is not None:
+        _need(prior, torch.float32, "prior", D * KS)
+    if any(t.device != dev for t in (pair_word, pair_cnt, doc_pair_ptr) + (() if prior is None else (prior,))):
+        raise ValueError("vfold: every tensor must be on the table's device")
+    if not _is_dev(table):
+        th, g = vfold_spec.vfold(pair_word.numpy(), pair_cnt.numpy(), doc_pair_ptr.numpy(), table.numpy(), K,
+                                 float(alpha), None if prior is None else prior.numpy().reshape(D, KS), iters)
+        th, g = torch.from_numpy(th.astype(np.float32)), torch.from_numpy(g.astype(np.float32))
+        return (th, g) if want_gamma else th
+    theta = torch.empty(D, KS, dtype=torch.float32, device=dev)
+    gamma = torch.empty(D, KS, dtype=torch.float32, device=dev) if want_gamma else None
+    _lib.check(_lib.lib().oni_vfold(_lib.ptr(pair_word) if P else None, _lib.ptr(pair_cnt) if P else None,
+                                    _lib.ptr(doc_pair_ptr), D, _lib.ptr(table), KS, K, float(np.float32(alpha)),
+                                    _lib.ptr(prior), iters, _lib.ptr(theta) if D else None, _lib.ptr(gamma),
+                                    _lib.stream()), "oni_vfold")
+    return (theta, gamma) if want_gamma else theta

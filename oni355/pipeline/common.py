@@ -1132,20 +1132,30 @@ def top_list_mismatch(model, top_domains, user_domain: str | None, log=None) -> 
     return bool(bad)
 
 
+def check_infer_method(method: str, iters: int) -> None:
+    """The ``method`` / ``iters`` arguments of the score_* functions."""
+    if method not in ("gibbs", "vb"):
+        raise ValueError('method must be "gibbs" or "vb"')
+    if method == "vb" and int(iters) < 0:
+        raise ValueError("iters must be ≥ 0")
+
+
 @traced("oni:score_single_doc_events")
 def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, model, tol: float, maxresults: int,
                             sweeps: int, avg_last: int, seed: int, chunk_len: int, row_offset: int,
                             timer: StageTimer, fuse: bool = True, prior_mass: float = 0.0,
-                            fit: bool = False) -> SingleResult:
+                            fit: bool = False, method: str = "gibbs", iters: int = 20) -> SingleResult:
     """The DNS / proxy half of scoring against a saved model, after wordification: one (doc, word)
     token per event. Word ids through the model's vocabulary (an unseen word → id V, the
     out-of-vocabulary row), the batch's own documents folded in against the frozen table
     (models.foldin.FoldIn, optionally under per-IP priors), θ, then the one-sided score plan and
     top-N against the model's table -- :func:`oni355.pipeline.flow.score_flow` for one endpoint.
-    ``fit``: also the batch's likelihood under the model (:func:`batch_fit`), in a ``fit`` stage."""
-    from ..models.foldin import FoldIn
+    ``fit``: also the batch's likelihood under the model (:func:`batch_fit`), in a ``fit`` stage.
+    ``method`` / ``iters``: ``"vb"`` takes θ from the variational fold-in (models.foldin.VarFoldIn)."""
+    from ..models.foldin import FoldIn, VarFoldIn
     from ..models.gibbs import tiling_for
     from ..ref.foldin_spec import V6_KEY_BASE
+    check_infer_method(method, iters)
     dev = doc_keys64.device
     n = int(doc_keys64.numel())
     with timer.stage("vocab"):
@@ -1175,8 +1185,11 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
                 pos = torch.searchsorted(mkeys, udoc).clamp_(max=int(mkeys.numel()) - 1)
                 n_prior = int(((mkeys[pos] == udoc) & (udoc < V6_KEY_BASE)).sum())
     with timer.stage("foldin"):
-        fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
-        fold.run(sweeps, avg_last)
+        if method == "vb":
+            fold = VarFoldIn(corpus, table, K, model.alpha, prior=prior).run(iters)
+        else:
+            fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
+            fold.run(sweeps, avg_last)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     ids = None
     with timer.stage("score_prep"):
@@ -1205,6 +1218,8 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
     stats = corpus.stats()
     stats.update({"events": n, "loglik": None, "mode": "infer", "n_oov_tokens": int(oov.item()),
                   "foldin_launches": sum(fold.launches.values())})
+    if method == "vb":
+        stats.update({"infer_method": "vb", "infer_iters": int(iters)})
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
     if bfit is not None:

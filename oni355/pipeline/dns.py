@@ -169,12 +169,12 @@ def score_dns(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweep
               seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
               top_domains=None, user_domain: str | None = None, feedback: dict | None = None, chunk_len: int = 0,
               row_offset: int = 0, log=None, fuse: bool = True, prior_mass: float = 0.0,
-              fit: bool = False) -> common.SingleResult:
+              fit: bool = False, method: str = "gibbs", iters: int = 20) -> common.SingleResult:
     """Score a batch of DNS responses against a saved model (``model``: models.saved.SavedModel of
     source ``dns``) instead of training on it: words from the model's cuts, the given top-domain
     list and the model's user domain (``user_domain`` None; another list or domain is allowed and
     reported as ``model_top_mismatch``), then :func:`common.score_single_doc_events`.
-    ``prior_mass`` and ``fit``: as
+    ``prior_mass``, ``fit``, ``method`` and ``iters``: as
     :func:`oni355.pipeline.flow.score_flow`."""
     if comm is not None and comm.dist:
         raise NotImplementedError("fold-in scoring is single-GPU")
@@ -193,7 +193,7 @@ def score_dns(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweep
         words, _, feats = featurize(d, None, top_set(top_domains), user_domain, cuts=model.cuts)
     res = common.score_single_doc_events(common.u32_to_i64(d["ip_dst"]), words, model, tol, maxresults, sweeps,
                                          avg_last, seed, chunk_len, row_offset, timer, fuse=fuse,
-                                         prior_mass=prior_mass, fit=fit)
+                                         prior_mass=prior_mass, fit=fit, method=method, iters=iters)
     res.stats["model_top_mismatch"] = mismatch
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in model.cuts.items()}
     res.stats["features"] = feats

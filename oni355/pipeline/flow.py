@@ -334,7 +334,8 @@ model_word_ids = common.model_word_ids
 def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
                seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
                feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
-               fuse: bool = True, prior_mass: float = 0.0, fit: bool = False) -> FlowResult:
+               fuse: bool = True, prior_mass: float = 0.0, fit: bool = False, method: str = "gibbs",
+               iters: int = 20) -> FlowResult:
     """Score a batch of flows against a saved model (``model``: models.saved.SavedModel) instead of
     training on it: words from the model's cuts, ids through its vocabulary (unseen words → the
     out-of-vocabulary row), the batch's own IP documents folded in against the frozen φ
@@ -346,14 +347,20 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
 
     ``fit``: after scoring, a timed ``fit`` stage computes every IP's log-likelihood under the model
     and its fold-in θ and the batch totals (:func:`common.batch_fit`): ``FlowResult.fit`` and the
-    ``batch_*`` stats. Off, nothing of it runs."""
+    ``batch_*`` stats. Off, nothing of it runs.
+
+    ``method``: ``"gibbs"`` (the default) samples θ with the fold-in chain; ``"vb"`` computes it with
+    ``iters`` iterations of the deterministic variational fold-in (models.foldin.VarFoldIn):
+    ``sweeps``, ``avg_last`` and ``seed`` are then ignored and ``stats`` carries ``infer_method`` and
+    ``infer_iters``."""
     from ..models.corpus import auto_chunk_len, build_corpus
-    from ..models.foldin import FoldIn
+    from ..models.foldin import FoldIn, VarFoldIn
     from ..models.gibbs import tiling_for
     if comm is not None and comm.dist:
         raise NotImplementedError("fold-in scoring is single-GPU")
     if model.source != "flow":
         raise ValueError(f"a {model.source} model cannot score flows")
+    common.check_infer_method(method, iters)
     if feedback and log:
         log("analyst feedback is ignored when scoring against a saved model")
     prior_mass = float(prior_mass)
@@ -403,8 +410,11 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
                 pos = torch.searchsorted(mkeys, udoc).clamp_(max=int(mkeys.numel()) - 1)
                 n_prior = int(((mkeys[pos] == udoc) & (udoc < V6_KEY_BASE)).sum())
     with timer.stage("foldin"):
-        fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
-        fold.run(sweeps, avg_last)
+        if method == "vb":
+            fold = VarFoldIn(corpus, table, K, model.alpha, prior=prior).run(iters)
+        else:
+            fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
+            fold.run(sweeps, avg_last)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     ids = None
     with timer.stage("score_prep"):
@@ -438,6 +448,8 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
     # the miss counter of the vocabulary lookup is read here, with the result rows
     stats.update({"n_flows": n, "loglik": None, "mode": "infer", "n_oov_tokens": int(oov.item()),
                   "foldin_launches": sum(fold.launches.values())})
+    if method == "vb":
+        stats.update({"infer_method": "vb", "infer_iters": int(iters)})
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
     if bfit is not None:

@@ -266,12 +266,13 @@ def model_from_result(res: common.SingleResult, top_domains=None, cfg: dict | No
 def score_proxy(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweeps: int = 30, avg_last: int = 10,
                 seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
                 top_domains=None, feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
-                fuse: bool = True, prior_mass: float = 0.0, fit: bool = False) -> common.SingleResult:
+                fuse: bool = True, prior_mass: float = 0.0, fit: bool = False, method: str = "gibbs",
+                iters: int = 20) -> common.SingleResult:
     """Score a batch of proxy requests against a saved model (``model``: models.saved.SavedModel of
     source ``proxy``) instead of training on it: words from the model's cuts and its user-agent
     frequency table (a user agent the training day never saw counts 0) and the given top-domain
     list (another list than the model's is allowed and reported as ``model_top_mismatch``), then
-    :func:`common.score_single_doc_events`. ``prior_mass`` and ``fit``: as
+    :func:`common.score_single_doc_events`. ``prior_mass``, ``fit``, ``method`` and ``iters``: as
     :func:`oni355.pipeline.flow.score_flow`."""
     if comm is not None and comm.dist:
         raise NotImplementedError("fold-in scoring is single-GPU")
@@ -291,7 +292,7 @@ def score_proxy(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swe
         words, _, _ = featurize(cols, device, None, top_set(top_domains), d=d, day=(model.cuts, ua))
     res = common.score_single_doc_events(common.u32_to_i64(d["clientip"]), words, model, tol, maxresults, sweeps,
                                          avg_last, seed, chunk_len, row_offset, timer, fuse=fuse,
-                                         prior_mass=prior_mass, fit=fit)
+                                         prior_mass=prior_mass, fit=fit, method=method, iters=iters)
     res.stats["model_top_mismatch"] = mismatch
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in model.cuts.items()}
     return res
