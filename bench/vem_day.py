@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Whole days of Gibbs and variational-EM training alternating in ONE process on ONE generated day:
+
+  gibbs   run_flow / run_dns at the bench.py default shape (the collapsed-Gibbs sampler)
+  vem     the same day with method="vem" (models.vem_gpu.VarLDA: --em-iters × --var-iters)
+
+  python bench/vem_day.py --flows 12500000 --topics 20 --rounds 3 --out profiles/vem/flow_k20.json
+  python bench/vem_day.py --source dns --flows 2000000 --topics 50 --out profiles/vem/dns_k50.json
+
+Prints one JSON line per day (ms per day, ms of the train stage, planted recall in the top-N) and a
+summary with the median / min / spread of each variant. After the timed days, untimed:
+
+  * the likelihood trace of one vem day per EM iteration (eval_every=1);
+  * the split of one EM iteration, each op timed alone with device events on the last vem day's
+    corpus (median of --op-reps): E-step (ops.vfold), resp, wsum, table;
+  * the overlap of the vem day's top-N with the Gibbs days' and the Gibbs days' among themselves
+    (every Gibbs round runs its own seed).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def op_split(model, reps: int) -> dict:
+    """Median device ms of the four ops of one EM iteration on ``model``'s corpus and table."""
+    import torch
+
+    from oni355 import ops
+    pw, pc, ptr = model._pairs
+    wm_ptr, wm_doc, wm_word, wm_pos = ops.vem_word_major(pw, model._pair_doc, model.V)
+    _, gamma = ops.vfold(pw, pc, ptr, model.table, model.K, model.alpha, None, model.var_iters, want_gamma=True)
+    e, q = ops.vem_resp(gamma, model.table, model._pair_doc, pw, pc, model.K, wm_pos)
+    ss = ops.vem_wsum(e, q, model.table, wm_ptr, wm_doc, wm_word, model.V, model.K)
+    steps = {"estep": lambda: ops.vfold(pw, pc, ptr, model.table, model.K, model.alpha, None, model.var_iters, want_gamma=True),
+             "resp": lambda: ops.vem_resp(gamma, model.table, model._pair_doc, pw, pc, model.K, wm_pos),
+             "wsum": lambda: ops.vem_wsum(e, q, model.table, wm_ptr, wm_doc, wm_word, model.V, model.K),
+             "table": lambda: ops.vem_table(ss, model.K, model.beta)}
+    out = {}
+    for name, fn in steps.items():
+        ms = []
+        for _ in range(reps + 2):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        ms = ms[2:]  # the first two warm the caches and the allocator
+        out[name] = {"ms_median": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4),
+                     "ms_spread": round(max(ms) - min(ms), 4)}
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--flows", type=int, default=12_500_000)
+    ap.add_argument("--topics", type=int, default=20)
+    ap.add_argument("--sweeps", type=int, default=200, help="Gibbs sweeps")
+    ap.add_argument("--em-iters", type=int, default=30)
+    ap.add_argument("--var-iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--maxresults", type=int, default=3000)
+    ap.add_argument("--op-reps", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--source", choices=["flow", "dns"], default="flow")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+
+    dev = torch.device(a.device)
+    t0 = time.perf_counter()
+    kw = dict(K=a.topics, tol=1.0, maxresults=a.maxresults, device=dev)
+    if a.source == "flow":
+        from oni355.pipeline.flow import run_flow as run
+        from oni355.synth.flow import generate_flows
+        day = generate_flows(a.flows, seed=a.seed, n_hosts=max(64, a.flows // 25))
+    else:
+        from oni355.pipeline import dns
+        from oni355.synth.dns import generate_dns
+        day = generate_dns(a.flows, seed=a.seed, n_clients=max(32, a.flows // 40))
+
+        def run(cols, **k):
+            return dns.run_dns(cols, user_domain="intel", **k)
+    planted = set(np.asarray(day.anomaly_rows).tolist())
+    print(f"generated {a.flows} {a.source} events in {time.perf_counter() - t0:.1f} s", flush=True)
+    vkw = dict(method="vem", em_iters=a.em_iters, var_iters=a.var_iters)
+    variants = {"gibbs": lambda r: run(day.cols, sweeps=a.sweeps, seed=101 + r, **kw),
+                "vem": lambda r: run(day.cols, **vkw, **kw)}
+    for fn in variants.values():  # one untimed day each: allocator, graphs, code objects
+        fn(0)
+    days = {n: [] for n in variants}
+    tops = {n: [] for n in variants}
+    last_vem = None
+    for r in range(a.rounds):
+        for name, fn in variants.items():
+            torch.cuda.synchronize(dev)
+            ts = time.perf_counter()
+            res = fn(r)
+            torch.cuda.synchronize(dev)
+            wall = time.perf_counter() - ts
+            t = res.timings
+            train_ms = t.get("train_dev_s", t.get("train_s", 0.0)) * 1e3
+            rows = set(res.rows.tolist())
+            line = {"variant": name, "round": r, "day_ms": round(wall * 1e3, 2), "train_ms": round(train_ms, 3),
+                    "init_ms": round(t.get("init_dev_s", t.get("init_s", 0.0)) * 1e3, 3),
+                    "ms_per_iter": round(train_ms / max(a.em_iters if name == "vem" else a.sweeps, 1), 4),
+                    "planted_recall_topN": round(len(rows & planted) / max(len(planted), 1), 4),
+                    "loglik": res.stats["loglik"]}
+            days[name].append(line)
+            tops[name].append(rows)
+            print(json.dumps(line), flush=True)
+            if name == "vem":
+                last_vem = res.lda.model
+            del res
+
+    def summ(v):
+        d, s = [x["day_ms"] for x in v], [x["ms_per_iter"] for x in v]
+        return {"day_ms_median": statistics.median(d), "day_ms_min": min(d), "day_ms_spread": round(max(d) - min(d), 2),
+                "ms_per_iter_median": statistics.median(s), "ms_per_iter_min": min(s),
+                "ms_per_iter_spread": round(max(s) - min(s), 4),
+                "planted_recall_topN": [x["planted_recall_topN"] for x in v]}
+    summary = {n: summ(v) for n, v in days.items()}
+    n_top = max(len(tops["vem"][0]), 1)
+    g = tops["gibbs"]
+    overlap = {"vem_vs_vem": [round(len(tops["vem"][0] & x) / n_top, 4) for x in tops["vem"][1:]],
+               "vem_vs_gibbs": [round(len(tops["vem"][0] & x) / n_top, 4) for x in g],
+               "gibbs_vs_gibbs": [round(len(g[i] & g[j]) / n_top, 4) for i in range(len(g)) for j in range(i + 1, len(g))]}
+    split = op_split(last_vem, a.op_reps)
+    traced = run(day.cols, eval_every=1, **vkw, **kw)
+    trace = [[int(i), float(ll)] for i, ll in traced.lda.model.likelihoods]
+    out = {"source": a.source, "flows": a.flows, "topics": a.topics, "gibbs_sweeps": a.sweeps, "em_iters": a.em_iters,
+           "var_iters": a.var_iters, "rounds": a.rounds,
+           "stats": {k: v for k, v in traced.stats.items() if isinstance(v, (int, float, str))},
+           "summary": summary, "top_overlap": overlap, "op_split_ms": split, "loglik_trace": trace, "days": days}
+    print(json.dumps({"summary": summary, "top_overlap": overlap, "op_split_ms": split}), flush=True)
+    print(json.dumps({"loglik_trace": trace}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

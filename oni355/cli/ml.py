@@ -71,6 +71,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--infer-prior-mass", type=float, default=0.0, metavar="M",
                     help="--model: fold an IP the model knows in under its training-day topic profile, weighted "
                          "by at most M pseudo-tokens (0: off, every IP starts from the flat prior)")
+    ap.add_argument("--train-method", choices=["gibbs", "vem"], default="gibbs",
+                    help="how the day's model is trained: gibbs (default, the collapsed-Gibbs sampler) or vem "
+                         "(variational EM, lda-c's estimator: deterministic, no seed, single GPU; --sweeps unused)")
+    ap.add_argument("--em-iters", type=int, default=None, metavar="N",
+                    help="--train-method vem: EM iterations (default 30)")
+    ap.add_argument("--var-iters", type=int, default=None, metavar="N",
+                    help="--train-method vem: E-step iterations per EM iteration (default 20, lda-c's var max iter; "
+                         "score the saved model with --infer-method vb --infer-iters N to reproduce the day's topic mixes)")
     ap.add_argument("--burnin", type=int, default=None, help="sweeps before the likelihood trace / snapshots")
     ap.add_argument("--max-restarts", type=int, default=0,
                     help="supervise the run: after a failure (crash, watchdog exit, numerical fault) start a "
@@ -258,6 +266,20 @@ def main(argv=None) -> int:
         opt = "--model" if a.model else "--save-model"
         if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
+    for flag, val in (("--em-iters", a.em_iters), ("--var-iters", a.var_iters)):
+        if val is not None and a.train_method != "vem":
+            raise SystemExit(f"oni-ml: {flag} belongs to variational EM; it needs --train-method vem")
+        if val is not None and val < 0:
+            raise SystemExit(f"oni-ml: {flag} must be ≥ 0")
+    if a.train_method == "vem":
+        if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("oni-ml: --train-method vem is single-GPU; drop --gpus")
+        for flag, val in (("--ckpt-dir", a.ckpt_dir), ("--ldac-out", a.ldac_out), ("--model", a.model)):
+            if val:
+                raise SystemExit(f"oni-ml: --train-method vem does not combine with {flag} (no checkpoints, no lda-c "
+                                 "files, and --model trains nothing)")
+        if a.max_restarts > 0:
+            raise SystemExit("oni-ml: --train-method vem does not combine with --max-restarts (no checkpoints)")
     if a.infer_fit and not a.model:
         raise SystemExit("oni-ml: --infer-fit reports the fit of a saved model; it needs --model FILE")
     for flag, val in (("--infer-method", a.infer_method), ("--infer-iters", a.infer_iters)):
@@ -334,6 +356,9 @@ def main(argv=None) -> int:
                      beta=cfg.BETA, seed=cfg.SEED, chunk_len=cfg.CHUNK_LEN, device=device, comm=comm, feedback=fb,
                      dupfactor=cfg.DUPFACTOR, row_offset=row_off, eval_every=cfg.EVAL_EVERY, burnin=cfg.BURNIN,
                      ckpt=ckpt, log=log)
+    if a.train_method == "vem":
+        common_kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
+                         var_iters=20 if a.var_iters is None else a.var_iters)
     if a.ldac_out and a.ldac_lag > 0:
         common_kw.update(ldac_dir=os.path.join(a.ldac_out, f"rank{rank}") if world > 1 else a.ldac_out,
                          ldac_lag=a.ldac_lag)
@@ -430,6 +455,9 @@ def _main_days(a, cfg, comm, device, dates: list[str], log) -> int:
     kw = dict(K=cfg.TOPIC_COUNT, sweeps=cfg.SWEEPS, tol=cfg.TOL, maxresults=cfg.MAXRESULTS, alpha=alpha,
               beta=cfg.BETA, seed=cfg.SEED, chunk_len=cfg.CHUNK_LEN, device=device, dupfactor=cfg.DUPFACTOR,
               eval_every=cfg.EVAL_EVERY, burnin=cfg.BURNIN, log=log)
+    if a.train_method == "vem":
+        kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
+                  var_iters=20 if a.var_iters is None else a.var_iters)
     if a.source == "dns":
         kw.update(top_domains=top, user_domain=cfg.USER_DOMAIN)
     elif a.source == "proxy":

@@ -161,8 +161,14 @@ class SavedModel:
         if run.route is not None or run.extra_models:
             raise NotImplementedError("models are saved from single-GPU, single-chain runs")
         K = m.K
-        prv = {"sweeps": int(m.sweeps_done), "seed": int(m.cfg.seed), "tree_hash": prov.tree_hash("hip"),
-               "averaged": m._averaged() is not None}
+        if hasattr(m, "phi_oov"):  # variational EM (models.vem_gpu.VarLDA): no seed, its own unseen-word row
+            prv = {"train_method": "vem", "em_iters": int(m.sweeps_done), "var_iters": int(m.var_iters),
+                   "tree_hash": prov.tree_hash("hip")}
+            phi_oov = m.phi_oov().cpu().numpy()
+        else:
+            prv = {"sweeps": int(m.sweeps_done), "seed": int(m.cfg.seed), "tree_hash": prov.tree_hash("hip"),
+                   "averaged": m._averaged() is not None}
+            phi_oov = oov_row(m)
         prv.update(cfg or {})
         prof = {}
         if docs:
@@ -179,7 +185,7 @@ class SavedModel:
         if ua_table is not None:
             prof.update(ua_keys=_host(ua_table[0]), ua_counts=_host(ua_table[1]))
         return cls(source=source, K=K, alpha=float(m.alpha), beta=float(m.beta),
-                   vocab=run.vocab.cpu().numpy(), phi=m.phi()[:, :K].cpu().numpy(), phi_oov=oov_row(m),
+                   vocab=run.vocab.cpu().numpy(), phi=m.phi()[:, :K].cpu().numpy(), phi_oov=phi_oov,
                    cuts=cuts, provenance=prv, **prof)
 
     def save(self, path: str) -> str:

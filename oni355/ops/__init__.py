@@ -1280,3 +1280,122 @@ def vfold(pair_word: torch.Tensor, pair_cnt: torch.Tensor, doc_pair_ptr: torch.T
                                     _lib.ptr(prior), iters, _lib.ptr(theta) if D else None, _lib.ptr(gamma),
                                     _lib.stream()), "oni_vfold")
     return (theta, gamma) if want_gamma else theta
+
+
+# ------------------------------------------------------------------------------------------------
+# variational EM (csrc/kernels/vem.hip): the M-step around vfold's E-step
+# ------------------------------------------------------------------------------------------------
+def _vem_ks(table: torch.Tensor, K: int, what: str) -> int:
+    _need(table, torch.float32, "table")
+    if table.dim() != 2 or table.shape[1] % 4 or table.shape[1] > 256 or not 1 <= int(K) <= table.shape[1]:
+        raise ValueError(f"{what}: table f32 [rows, KS], KS a multiple of 4 up to 256, 1 ≤ K ≤ KS")
+    return int(table.shape[1])
+
+
+def vem_word_major(pair_word: torch.Tensor, pair_doc: torch.Tensor, V: int):
+    """The word-major pair order :func:`vem_wsum` sums over, built once per model: (word_pair_ptr
+    int64 [V + 1], wm_doc int32 [P], wm_word int32 [P], wm_pos int32 [P]); ``wm_pos[p]`` is the
+    word-major position of doc-major pair p. Stable sort: a word's pairs keep their document order."""
+    _need(pair_word, torch.int32, "pair_word")
+    _need(pair_doc, torch.int32, "pair_doc", int(pair_word.numel()))
+    wm_word, order = torch.sort(pair_word, stable=True)
+    pos = torch.empty_like(pair_word)
+    pos[order] = torch.arange(pair_word.numel(), dtype=torch.int32, device=pair_word.device)
+    ptr = torch.zeros(int(V) + 1, dtype=torch.int64, device=pair_word.device)
+    if pair_word.numel():
+        torch.cumsum(torch.bincount(pair_word.long(), minlength=int(V))[: int(V)], 0, out=ptr[1:])
+    return ptr, pair_doc[order].contiguous(), wm_word.contiguous(), pos
+
+
+def vem_resp(gamma: torch.Tensor, table: torch.Tensor, pair_doc: torch.Tensor, pair_word: torch.Tensor,
+             pair_cnt: torch.Tensor, K: int, wm_pos: torch.Tensor | None = None):
+    """Responsibilities from the E-step's final γ (k_vem_e, k_vem_q): e f32 [D, KS] =
+    exp(ψ(γ) − row max ψ), zero past K, and q f32 [P] = count / (table row · e row) of every doc-major
+    pair, written at ``wm_pos`` (int32 [P], a permutation: the word-major order of
+    :func:`vem_word_major`) when given. CPU tensors run :func:`oni355.ref.vem_spec.resp` in float64,
+    rounded to f32."""
+    from ..ref import vem_spec
+    KS, K, P = _vem_ks(table, K, "vem_resp"), int(K), int(pair_doc.numel())
+    _need(gamma, torch.float32, "gamma")
+    if gamma.dim() != 2 or gamma.shape[1] != KS:
+        raise ValueError("vem_resp: gamma f32 [D, KS] with the table's KS")
+    D = int(gamma.shape[0])
+    for t, nm in ((pair_doc, "pair_doc"), (pair_word, "pair_word"), (pair_cnt, "pair_cnt")) + \
+            (((wm_pos, "wm_pos"),) if wm_pos is not None else ()):
+        _need(t, torch.int32, nm, P)
+        if t.device != table.device:
+            raise ValueError("vem_resp: every tensor must be on the table's device")
+    if gamma.device != table.device:
+        raise ValueError("vem_resp: every tensor must be on the table's device")
+    if not _is_dev(table):
+        e, q = vem_spec.resp(gamma.numpy(), table.numpy(), pair_doc.numpy(), pair_word.numpy(), pair_cnt.numpy(), K)
+        if wm_pos is not None:
+            qw = np.empty_like(q)
+            qw[wm_pos.numpy()] = q
+            q = qw
+        return torch.from_numpy(e.astype(np.float32)), torch.from_numpy(q.astype(np.float32))
+    e = torch.empty(D, KS, dtype=torch.float32, device=table.device)
+    q = torch.empty(P, dtype=torch.float32, device=table.device)
+    _lib.check(_lib.lib().oni_vem_resp(_lib.ptr(gamma) if D else None, _lib.ptr(table), int(table.shape[0]), KS, K,
+                                       _lib.ptr(pair_doc) if P else None, _lib.ptr(pair_word) if P else None,
+                                       _lib.ptr(pair_cnt) if P else None, _lib.ptr(wm_pos) if P else None, P, D,
+                                       _lib.ptr(e) if D else None, _lib.ptr(q) if P else None, _lib.stream()),
+               "oni_vem_resp")
+    return e, q
+
+
+def vem_wsum(e: torch.Tensor, q: torch.Tensor, table: torch.Tensor, word_pair_ptr: torch.Tensor, wm_doc: torch.Tensor,
+             wm_word: torch.Tensor, V: int, K: int, grid: int | None = None) -> torch.Tensor:
+    """Sufficient statistics ss f32 [V, KS] = table[w,k] · Σ_{pairs of w} q · e[doc, k] (k_vem_wsum,
+    k_vem_wcomb): a segmented sum over the word-major pair list of :func:`vem_word_major` (``q``
+    f32 [P] in that order), accumulated in f64 and rounded once. Same inputs, same bits, whatever
+    ``grid`` (blocks per pass; default sized from P and V). CPU tensors run
+    :func:`oni355.ref.vem_spec.wsum` in float64, rounded to f32."""
+    from ..ref import vem_spec
+    KS, K, V, P = _vem_ks(table, K, "vem_wsum"), int(K), int(V), int(q.numel())
+    _need(e, torch.float32, "e")
+    _need(q, torch.float32, "q")
+    _need(word_pair_ptr, torch.int64, "word_pair_ptr", V + 1)
+    _need(wm_doc, torch.int32, "wm_doc", P)
+    _need(wm_word, torch.int32, "wm_word", P)
+    if e.dim() != 2 or e.shape[1] != KS or table.shape[0] < V + 1 or V < 1:
+        raise ValueError("vem_wsum: e f32 [D, KS] and table f32 [V + 1, KS] with one KS, V ≥ 1")
+    if any(t.device != table.device for t in (e, q, word_pair_ptr, wm_doc, wm_word)):
+        raise ValueError("vem_wsum: every tensor must be on the table's device")
+    if grid is not None and not 1 <= int(grid) <= 65535:
+        raise ValueError("vem_wsum: grid must be in [1, 65535]")
+    if not _is_dev(table):
+        return torch.from_numpy(vem_spec.wsum(e.numpy(), q.numpy(), table.numpy(), word_pair_ptr.numpy(),
+                                              wm_doc.numpy(), K).astype(np.float32))
+    D = int(e.shape[0])
+    ss = torch.empty(V, KS, dtype=torch.float32, device=table.device)
+    # a head and a tail partial of KS doubles per span of 256 pairs: never initialised
+    scratch = torch.empty(max(2 * ((P + 255) // 256) * KS, 1), dtype=torch.float64, device=table.device)
+    _lib.check(_lib.lib().oni_vem_wsum(_lib.ptr(e) if D else None, _lib.ptr(q) if P else None,
+                                       _lib.ptr(wm_doc) if P else None, _lib.ptr(wm_word) if P else None,
+                                       _lib.ptr(word_pair_ptr), _lib.ptr(table), P, D, V, KS, K, _lib.ptr(ss),
+                                       _lib.ptr(scratch), int(grid or 0), _lib.stream()), "oni_vem_wsum")
+    return ss
+
+
+def vem_table(ss: torch.Tensor, K: int, beta: float, grid: int | None = None):
+    """The M-step's table from the statistics ``ss`` f32 [V, KS] (k_vem_colpart, k_vem_coltot,
+    k_vem_rows): (table f32 [V + 1, KS], ss_k f64 [KS]) with table = (ss + β)/(ss_k + Vβ), row V =
+    β/(ss_k + Vβ), zero past K; f64 arithmetic rounded once, column totals in a fixed order. CPU
+    tensors run :func:`oni355.ref.vem_spec.table` in float64, the table rounded to f32."""
+    from ..ref import vem_spec
+    KS, K, beta = _vem_ks(ss, K, "vem_table"), int(K), float(beta)
+    V = int(ss.shape[0])
+    if V < 1 or not beta > 0:
+        raise ValueError("vem_table: ss f32 [V, KS] with V ≥ 1, beta > 0")
+    if grid is not None and not 1 <= int(grid) <= 65535:
+        raise ValueError("vem_table: grid must be in [1, 65535]")
+    if not _is_dev(ss):
+        t, ssk = vem_spec.table(ss.numpy(), K, beta)
+        return torch.from_numpy(t.astype(np.float32)), torch.from_numpy(ssk)
+    table = torch.empty(V + 1, KS, dtype=torch.float32, device=ss.device)
+    ssk = torch.empty(KS, dtype=torch.float64, device=ss.device)
+    part = torch.empty(((V + 255) // 256) * KS, dtype=torch.float64, device=ss.device)
+    _lib.check(_lib.lib().oni_vem_table(_lib.ptr(ss), V, KS, K, beta, _lib.ptr(table), _lib.ptr(ssk), _lib.ptr(part),
+                                        int(grid or 0), _lib.stream()), "oni_vem_table")
+    return table, ssk

@@ -546,8 +546,13 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                     chunk_len: int, comm: Comm | None, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None,
                     train: bool = True, timer: StageTimer | None = None, ldac_dir: str | None = None,
                     ldac_lag: int = 0, word_ids: torch.Tensor | None = None, n_event0: int = 0,
-                    on_train=None) -> LdaRun:
+                    on_train=None, method: str = "gibbs", em_iters: int = 30, var_iters: int = 20) -> LdaRun:
     """Token keys → owner routing → local corpus → Gibbs LDA trained for ``sweeps`` sweeps.
+
+    ``method`` ``"vem"`` trains the model by variational EM instead (models.vem_gpu.VarLDA:
+    ``em_iters`` EM iterations of ``var_iters`` E-step iterations each, single GPU, no seed):
+    ``sweeps``, ``seed``, ``burnin``, ONI_CHAINS, checkpoints, LAG snapshots and the MH burn-in
+    do not apply.
 
     ``word_ids`` (int32, from :func:`encode_words`) skips the vocabulary lookup of ``word_keys64``.
     Where :func:`fused_corpus` holds, ``doc_keys64`` may also be int32 u32 bits or the two int32
@@ -574,7 +579,7 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
         G, _ = tiling_for(K)
         mh = sampler_for(K) == "mh"
         # an MH model's first sweeps run the dense kernel on a corpus of the dense tiling
-        burn_mh = mh_burn_for(sweeps) if mh and train else 0
+        burn_mh = mh_burn_for(sweeps) if mh and train and method != "vem" else 0
         Gd = tiling_for(K, "dense")[0] if burn_mh else G
         if chunk_len <= 0:
             # the global (weighted) token count picks L -- before routing: the placement cuts
@@ -627,6 +632,9 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                                     weight=wt if use_w else None, pairs=pairs if dev.type == "cuda" else None)
         corpus = corpus_for(G)
         dcorpus = corpus_for(Gd) if Gd != G else None
+    if method == "vem":
+        return _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every,
+                          train, timer, log, on_train)
     # ONI_CHAINS = C > 1: C independent chains of sweeps // C sweeps each (same total sweep count),
     # scored by the average of their pair scores (LdaRun.pair_scores): the top-N then depends less
     # on any one chain's seed. Dense samplers only, no checkpointing.
@@ -710,6 +718,46 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                 run.extra_models.append(ChainEstimate(mc.theta(), mc.phi(), mc.sweeps_done))
                 del mc
     run.timings.update({"sweeps": sweeps * chains, "chains": chains})
+    return run
+
+
+def check_train_method(method: str, em_iters: int, var_iters: int, comm=None, ckpt=None, ldac_dir=None) -> None:
+    """``method`` of run_* : ``"gibbs"`` or ``"vem"``; what vem training does not combine with."""
+    if method not in ("gibbs", "vem"):
+        raise ValueError(f"method must be 'gibbs' or 'vem', not {method!r}")
+    if method == "vem":
+        if int(em_iters) < 0 or int(var_iters) < 0:
+            raise ValueError("em_iters and var_iters must be ≥ 0")
+        if comm is not None and comm.dist:
+            raise NotImplementedError("vem training is single-GPU")
+        if ckpt is not None or ldac_dir:
+            raise ValueError("vem training writes no checkpoints and no lda-c snapshots")
+
+
+def vem_stats(method: str, em_iters: int, var_iters: int) -> dict:
+    """What ``stats`` gains in vem mode (nothing with the Gibbs sampler)."""
+    if method != "vem":
+        return {}
+    return {"train_method": "vem", "em_iters": int(em_iters), "var_iters": int(var_iters)}
+
+
+def _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every, train,
+               timer, log, on_train) -> LdaRun:
+    """The ``init`` / ``train`` stages of :func:`build_and_train` with ``method="vem"``."""
+    from ..models.vem_gpu import VarLDA
+    with timer.stage("init"):
+        model = VarLDA(corpus, K, alpha, beta, comm=comm)
+        run = LdaRun(corpus, model, udoc, vocab, {}, pairs=pairs, route=route)
+        if not train:
+            return run
+    with timer.stage("train"):
+        if on_train is not None:
+            on_train()
+        model.run(em_iters, var_iters, eval_every=eval_every, log=log)
+    model.close()
+    if not model.likelihoods or model.likelihoods[-1][0] != model.sweeps_done:
+        model.record_likelihood()
+    run.timings.update({"sweeps": model.sweeps_done, "chains": 1})
     return run
 
 
@@ -1048,8 +1096,10 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
                           maxresults: int, alpha, beta: float, seed: int, chunk_len: int, comm: Comm | None,
                           feedback=None, row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None,
                           timer: StageTimer | None = None, ldac_dir: str | None = None,
-                          ldac_lag: int = 0, key_bits: int = 64) -> SingleResult:
+                          ldac_lag: int = 0, key_bits: int = 64, method: str = "gibbs", em_iters: int = 30,
+                          var_iters: int = 20) -> SingleResult:
     """Shared DNS/proxy path: one (doc, word) token per event; score = θ_doc·φ_word (C24)."""
+    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir)
     dev = doc_keys64.device
     timer = timer or StageTimer(dev)
     with timer.stage("vocab"):
@@ -1065,7 +1115,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     n = int(doc_keys64.numel())
     run = build_and_train(dk, None, wts, vocab, K, alpha, beta, seed, sweeps, chunk_len, comm, eval_every=eval_every, burnin=burnin,
                           ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag, word_ids=wids,
-                          n_event0=n)
+                          n_event0=n, method=method, em_iters=em_iters, var_iters=var_iters)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     if run.route is not None:
         with timer.stage("score_prep"):
@@ -1092,6 +1142,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     stats = run.corpus.stats()
     stats.update({"events": int(doc_keys64.numel()),
                   "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
+    stats.update(vem_stats(method, em_iters, var_iters))
     return SingleResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(),
                         words=words.cpu().numpy().view(np.uint64), timings=t, stats=stats, lda=run)
 
