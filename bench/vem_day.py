@@ -15,6 +15,14 @@ summary with the median / min / spread of each variant. After the timed days, un
     corpus (median of --op-reps): E-step (ops.vfold), resp, wsum, table;
   * the overlap of the vem day's top-N with the Gibbs days' and the Gibbs days' among themselves
     (every Gibbs round runs its own seed).
+
+``--em-tol X`` runs another comparison instead (no Gibbs days): the fixed ``--em-iters`` day, the day
+with ``em_tol=X`` (at most ``--em-max`` iterations) and the fixed day with ``estimate_alpha``,
+alternating in one process; per variant the iterations run, ms per day, the final variational bound,
+the overlap of its top-N with the fixed day's and the planted recall; the α trace; and ops.vem_bound
+timed alone with device events next to ops.doc_fit on the same pairs.
+
+  python bench/vem_day.py --em-tol 1e-4 --out profiles/vem/bound_flow_12.5M_k20.json
 """
 from __future__ import annotations
 
@@ -58,6 +66,78 @@ def op_split(model, reps: int) -> dict:
     return out
 
 
+def _timed(fn, reps: int) -> dict:
+    import torch
+    ms = []
+    for _ in range(reps + 2):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms = ms[2:]  # the first two warm the caches and the allocator
+    return {"ms_median": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4),
+            "ms_spread": round(max(ms) - min(ms), 4)}
+
+
+def bound_ab(a, run, day, kw: dict, planted: set, dev) -> int:
+    """The ``--em-tol`` comparison of the module text."""
+    import torch
+
+    from oni355 import ops
+    base = dict(method="vem", var_iters=a.var_iters, **kw)
+    variants = {"fixed": dict(em_iters=a.em_iters), "tol": dict(em_iters=a.em_max, em_tol=a.em_tol),
+                "alpha": dict(em_iters=a.em_iters, estimate_alpha=True)}
+    for v in variants.values():  # one untimed day each
+        run(day.cols, **v, **base)
+    days = {n: [] for n in variants}
+    tops, models = {}, {}
+    for r in range(a.rounds):
+        for name, v in variants.items():
+            torch.cuda.synchronize(dev)
+            ts = time.perf_counter()
+            res = run(day.cols, **v, **base)
+            torch.cuda.synchronize(dev)
+            wall = time.perf_counter() - ts
+            m, rows = res.lda.model, set(res.rows.tolist())
+            line = {"variant": name, "round": r, "day_ms": round(wall * 1e3, 2), "em_iters_done": int(m.sweeps_done),
+                    "train_ms": round(res.timings.get("train_dev_s", res.timings.get("train_s", 0.0)) * 1e3, 3),
+                    "bound": m.bound(), "loglik": res.stats["loglik"], "alpha": float(m.alpha),
+                    "planted_recall_topN": round(len(rows & planted) / max(len(planted), 1), 4)}
+            days[name].append(line)
+            tops[name], models[name] = rows, m
+            print(json.dumps(line), flush=True)
+            del res
+    n_top = max(len(tops["fixed"]), 1)
+    summary = {n: {"day_ms_median": statistics.median(x["day_ms"] for x in v),
+                   "day_ms_spread": round(max(x["day_ms"] for x in v) - min(x["day_ms"] for x in v), 2),
+                   "em_iters_done": v[-1]["em_iters_done"], "bound": v[-1]["bound"], "alpha": v[-1]["alpha"],
+                   "planted_recall_topN": v[-1]["planted_recall_topN"],
+                   "top_overlap_with_fixed": round(len(tops[n] & tops["fixed"]) / n_top, 4)} for n, v in days.items()}
+    m = models["fixed"]
+    pw, pc, ptr = m._pairs
+    theta, gamma = ops.vfold(pw, pc, ptr, m.table, m.K, m.alpha, None, m.var_iters, want_gamma=True)
+    ops_ms = {"vem_bound": _timed(lambda: ops.vem_bound(gamma, m.table, m._pair_doc, pw, pc, m.K, m.alpha, ptr), a.op_reps),
+              # the same γ without pairs: the row pass (ψ, lgamma) with the document and total passes
+              "vem_bound_rows_only": _timed(lambda: ops.vem_bound(gamma, m.table, m._pair_doc[:0], pw[:0], pc[:0], m.K,
+                                                                  m.alpha, torch.zeros_like(ptr)), a.op_reps),
+              "doc_fit": _timed(lambda: ops.doc_fit(theta, m.table, m._pair_doc, pw, pc, m.c.D, m.V), a.op_reps),
+              "estep": _timed(lambda: ops.vfold(pw, pc, ptr, m.table, m.K, m.alpha, None, m.var_iters), a.op_reps)}
+    out = {"source": a.source, "flows": a.flows, "topics": a.topics, "em_iters": a.em_iters, "em_max": a.em_max,
+           "em_tol": a.em_tol, "var_iters": a.var_iters, "rounds": a.rounds, "pairs": int(pw.numel()), "docs": int(m.c.D),
+           "summary": summary, "ops_ms": ops_ms,
+           "bound_trace_tol": [list(b) for b in models["tol"].bounds],
+           "alpha_trace": [[int(i), float(al)] for i, _, _, al in models["alpha"].bounds] + [[int(models["alpha"].sweeps_done), float(models["alpha"].alpha)]],
+           "days": days}
+    print(json.dumps({"summary": summary, "ops_ms": ops_ms, "alpha_trace": out["alpha_trace"]}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--flows", type=int, default=12_500_000)
@@ -72,6 +152,8 @@ def main() -> int:
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--source", choices=["flow", "dns"], default="flow")
+    ap.add_argument("--em-tol", type=float, default=0.0, help="> 0: the convergence-exit / α comparison instead")
+    ap.add_argument("--em-max", type=int, default=100, help="--em-tol: the most EM iterations of the tol variant")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -92,6 +174,8 @@ def main() -> int:
             return dns.run_dns(cols, user_domain="intel", **k)
     planted = set(np.asarray(day.anomaly_rows).tolist())
     print(f"generated {a.flows} {a.source} events in {time.perf_counter() - t0:.1f} s", flush=True)
+    if a.em_tol > 0:
+        return bound_ab(a, run, day, kw, planted, dev)
     vkw = dict(method="vem", em_iters=a.em_iters, var_iters=a.var_iters)
     variants = {"gibbs": lambda r: run(day.cols, sweeps=a.sweeps, seed=101 + r, **kw),
                 "vem": lambda r: run(day.cols, **vkw, **kw)}

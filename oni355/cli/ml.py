@@ -79,6 +79,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--var-iters", type=int, default=None, metavar="N",
                     help="--train-method vem: E-step iterations per EM iteration (default 20, lda-c's var max iter; "
                          "score the saved model with --infer-method vb --infer-iters N to reproduce the day's topic mixes)")
+    ap.add_argument("--em-tol", type=float, default=None, metavar="X",
+                    help="--train-method vem: stop EM once the variational bound's relative change is in [0, X] "
+                         "(at least three iterations; --em-iters is then the maximum; default: run them all)")
+    ap.add_argument("--estimate-alpha", action="store_true",
+                    help="--train-method vem: re-estimate the symmetric alpha every EM iteration (lda-c's "
+                         "'alpha estimate'); the saved model carries the estimate")
     ap.add_argument("--burnin", type=int, default=None, help="sweeps before the likelihood trace / snapshots")
     ap.add_argument("--max-restarts", type=int, default=0,
                     help="supervise the run: after a failure (crash, watchdog exit, numerical fault) start a "
@@ -266,7 +272,8 @@ def main(argv=None) -> int:
         opt = "--model" if a.model else "--save-model"
         if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
-    for flag, val in (("--em-iters", a.em_iters), ("--var-iters", a.var_iters)):
+    for flag, val in (("--em-iters", a.em_iters), ("--var-iters", a.var_iters), ("--em-tol", a.em_tol),
+                      ("--estimate-alpha", a.estimate_alpha or None)):
         if val is not None and a.train_method != "vem":
             raise SystemExit(f"oni-ml: {flag} belongs to variational EM; it needs --train-method vem")
         if val is not None and val < 0:
@@ -358,7 +365,8 @@ def main(argv=None) -> int:
                      ckpt=ckpt, log=log)
     if a.train_method == "vem":
         common_kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
-                         var_iters=20 if a.var_iters is None else a.var_iters)
+                         var_iters=20 if a.var_iters is None else a.var_iters, em_tol=a.em_tol or 0.0,
+                         estimate_alpha=a.estimate_alpha)
     if a.ldac_out and a.ldac_lag > 0:
         common_kw.update(ldac_dir=os.path.join(a.ldac_out, f"rank{rank}") if world > 1 else a.ldac_out,
                          ldac_lag=a.ldac_lag)
@@ -457,7 +465,8 @@ def _main_days(a, cfg, comm, device, dates: list[str], log) -> int:
               eval_every=cfg.EVAL_EVERY, burnin=cfg.BURNIN, log=log)
     if a.train_method == "vem":
         kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
-                  var_iters=20 if a.var_iters is None else a.var_iters)
+                  var_iters=20 if a.var_iters is None else a.var_iters, em_tol=a.em_tol or 0.0,
+                  estimate_alpha=a.estimate_alpha)
     if a.source == "dns":
         kw.update(top_domains=top, user_domain=cfg.USER_DOMAIN)
     elif a.source == "proxy":

@@ -1,5 +1,5 @@
 """Variational-EM training on the device: the reference engine's own estimator (lda-c ``lda est``,
-smoothed, fixed α and β) as a second, seed-free train method beside the collapsed-Gibbs sampler.
+smoothed, fixed β) as a second, seed-free train method beside the collapsed-Gibbs sampler.
 
 One EM iteration is four ops over the corpus' distinct (doc, word, count) pairs: the E-step
 (``ops.vfold``, the kernel ``--infer-method vb`` scores with), the responsibilities
@@ -9,12 +9,18 @@ specification. Nothing is sampled: the same day gives the same model and the sam
 whatever the seed, and scoring the training day against the saved model with ``method="vb"``,
 ``iters=var_iters`` and no prior reproduces :meth:`VarLDA.theta`.
 
-Not done here: α estimation (lda-c's Newton step), the ELBO, warm-starting γ between EM iterations.
+Two options, both off by default, add a fifth op after the E-step, ``ops.vem_bound`` (the
+variational bound lda-c writes to likelihood.dat, and the α sufficient statistic), and read its two
+totals back: ``em_tol`` stops EM on the bound's relative change, ``estimate_alpha`` re-estimates
+the symmetric α by lda-c's Newton step after every table update.
+
+Not done here: warm-starting γ between EM iterations, a per-document E-step exit, vector α.
 """
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -51,22 +57,49 @@ class VarLDA:
         ss0[:, :self.K] = vem_spec.init_u(self.V, self.K, device=self.device) + 1.0 / self.V
         self.table, self.ss_k = ops.vem_table(ss0, self.K, self.beta)
         self._theta = None
+        self._gamma = None  # γ of the E-step θ came from, kept when the bound is tracked
         self.var_iters = VAR_ITERS
         self.sweeps_done = 0  # EM iterations done
         self.likelihoods: list = []
+        self.bounds: list = []  # (iteration, bound, conv, α the E-step ran with), one per tracked iteration
+        self.em_tol, self.estimate_alpha, self.converged = 0.0, False, False
 
     def _estep(self, want_gamma: bool):
         return ops.vfold(*self._pairs, self.table, self.K, self.alpha, None, self.var_iters, want_gamma=want_gamma)
 
+    def _bound(self, gamma: torch.Tensor) -> tuple[float, float]:
+        """(bound, α statistic) of an E-step's γ against the table and α it ran with: one launch
+        sequence and one 16-byte read."""
+        b = ops.vem_bound(gamma, self.table, self._pair_doc, self._pairs[0], self._pairs[1], self.K, self.alpha,
+                          self._pairs[2])
+        L, a_ss = b.tot.tolist()
+        if not math.isfinite(L):
+            raise fault.NumericalFault(f"non-finite variational bound {L} after EM iteration {self.sweeps_done}")
+        return L, a_ss
+
     @traced("oni:vem.run")
-    def run(self, em_iters: int = EM_ITERS, var_iters: int = VAR_ITERS, eval_every: int = 0, log=None) -> "VarLDA":
+    def run(self, em_iters: int = EM_ITERS, var_iters: int = VAR_ITERS, eval_every: int = 0, log=None,
+            em_tol: float = 0.0, estimate_alpha: bool = False) -> "VarLDA":
         """``em_iters`` rounds of E-step, responsibilities, statistics, table, then one final E-step
         against the final table. ``eval_every`` > 0 records the plug-in likelihood of every
-        ``eval_every``-th iteration's E-step (θ and the table it ran against)."""
+        ``eval_every``-th iteration's E-step (θ and the table it ran against).
+
+        With ``em_tol`` > 0 or ``estimate_alpha`` every E-step is followed by ``ops.vem_bound`` and
+        ``self.bounds`` gets (iteration, L, conv, α) with conv = (L_old − L)/L_old (1.0 for the
+        first). ``estimate_alpha``: after the table update α ← ``vem_spec.alpha_newton``, rounded
+        to float32 (what the E-step kernel and a saved model carry). ``em_tol`` > 0: ``em_iters``
+        is the maximum; EM stops after the M-step of an iteration that is at least the third of
+        this call and has 0 ≤ conv ≤ em_tol (lda-c's loop, without its doubling of the E-step
+        iterations on a negative conv). With both off nothing of this runs."""
         if em_iters < 0 or var_iters < 0:
             raise ValueError("em_iters and var_iters must be ≥ 0")
+        if not em_tol >= 0:
+            raise ValueError("em_tol must be ≥ 0")
         self.var_iters = int(var_iters)
+        self.em_tol, self.estimate_alpha, self.converged = float(em_tol), bool(estimate_alpha), False
+        track = self.em_tol > 0 or self.estimate_alpha
         ptr, wm_doc, wm_word, wm_pos = self._wm
+        L_old = 0.0
         for it in range(int(em_iters)):
             theta, gamma = self._estep(True)
             if eval_every > 0 and self.sweeps_done % eval_every == 0:
@@ -74,11 +107,27 @@ class VarLDA:
                 ll = self.record_likelihood()
                 if log:
                     log(f"em iteration {self.sweeps_done} loglik {ll:.6e}")
+            conv = 1.0
+            if track:
+                L, a_ss = self._bound(gamma)
+                conv = 1.0 if L_old == 0 else (L_old - L) / L_old
+                L_old = L
+                self.bounds.append((self.sweeps_done, L, conv, self.alpha))
+                if log:
+                    log(f"em iteration {self.sweeps_done} bound {L:.10e} conv {conv:.3e} alpha {self.alpha:.6g}")
             e, q = ops.vem_resp(gamma, self.table, self._pair_doc, self._pairs[0], self._pairs[1], self.K, wm_pos)
             ss = ops.vem_wsum(e, q, self.table, ptr, wm_doc, wm_word, self.V, self.K)
             self.table, self.ss_k = ops.vem_table(ss, self.K, self.beta)
+            if self.estimate_alpha:
+                self.alpha = float(np.float32(vem_spec.alpha_newton(a_ss, int(gamma.shape[0]), self.K)))
             self.sweeps_done += 1
-        self._theta = self._estep(False)
+            if self.em_tol > 0 and it + 1 >= 3 and 0 <= conv <= self.em_tol:
+                self.converged = True
+                break
+        if track:
+            self._theta, self._gamma = self._estep(True)
+        else:
+            self._theta, self._gamma = self._estep(False), None
         return self
 
     def theta(self) -> torch.Tensor:
@@ -86,6 +135,12 @@ class VarLDA:
         if self._theta is None:
             self._theta = self._estep(False)
         return self._theta
+
+    def bound(self) -> float:
+        """The variational bound of the final E-step (θ's) against the final table and α."""
+        if self._gamma is None:
+            self._theta, self._gamma = self._estep(True)
+        return self._bound(self._gamma)[0]
 
     def phi(self) -> torch.Tensor:
         """f32 [V, KS]: the table's first V rows."""

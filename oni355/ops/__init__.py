@@ -1399,3 +1399,56 @@ def vem_table(ss: torch.Tensor, K: int, beta: float, grid: int | None = None):
     _lib.check(_lib.lib().oni_vem_table(_lib.ptr(ss), V, KS, K, beta, _lib.ptr(table), _lib.ptr(ssk), _lib.ptr(part),
                                         int(grid or 0), _lib.stream()), "oni_vem_table")
     return table, ssk
+
+
+class VemBound(NamedTuple):
+    """What :func:`vem_bound` returns."""
+    doc: torch.Tensor  # f64 [D]: the variational bound L_d of every document
+    tot: torch.Tensor  # f64 [2]: Σ_d L_d and the α sufficient statistic Σ_d (Σ_k ψ(γ_dk) − K·ψ(Σ_k γ_dk))
+
+
+def vem_bound(gamma: torch.Tensor, table: torch.Tensor, pair_doc: torch.Tensor, pair_word: torch.Tensor,
+              pair_cnt: torch.Tensor, K: int, alpha: float, doc_pair_ptr: torch.Tensor | None = None,
+              grid: int | None = None) -> VemBound:
+    """The variational bound of lda-c's ``lda est`` and the α statistic from an E-step's γ
+    (csrc/kernels/vem_bound.hip: k_vbound_rows / _pairs / _docs / _total), all in f64 from the f32
+    inputs: ``gamma`` f32 [D, KS], ``table`` f32 [rows, KS], the doc-major pairs int32 [P]
+    (``pair_doc`` non-decreasing), ``alpha`` > 0 carried as f64, ``doc_pair_ptr`` int64 [D + 1] (the
+    pair range of every document; built from ``pair_doc`` when not given). A pair whose table row
+    has no mass under its document gives −inf for the document and the total; pairs naming a
+    document outside [0, D) or a word outside [0, rows) contribute nothing. Same inputs, same bits,
+    whatever ``grid`` (blocks per pass). CPU tensors run :func:`oni355.ref.vem_spec.bound`."""
+    from ..ref import vem_spec
+    KS, K, P, alpha = _vem_ks(table, K, "vem_bound"), int(K), int(pair_doc.numel()), float(alpha)
+    _need(gamma, torch.float32, "gamma")
+    if gamma.dim() != 2 or gamma.shape[1] != KS:
+        raise ValueError("vem_bound: gamma f32 [D, KS] with the table's KS")
+    if not alpha > 0:
+        raise ValueError("vem_bound: alpha must be > 0")
+    D, dev = int(gamma.shape[0]), table.device
+    for t, nm in ((pair_doc, "pair_doc"), (pair_word, "pair_word"), (pair_cnt, "pair_cnt")):
+        _need(t, torch.int32, nm, P)
+    if doc_pair_ptr is not None:
+        _need(doc_pair_ptr, torch.int64, "doc_pair_ptr", D + 1)
+    if any(t.device != dev for t in (gamma, pair_doc, pair_word, pair_cnt) + (() if doc_pair_ptr is None else (doc_pair_ptr,))):
+        raise ValueError("vem_bound: every tensor must be on the table's device")
+    if grid is not None and not 1 <= int(grid) <= 65535:
+        raise ValueError("vem_bound: grid must be in [1, 65535]")
+    if not _is_dev(table):
+        doc, tot = vem_spec.bound(gamma.numpy(), table.numpy(), pair_doc.numpy(), pair_word.numpy(), pair_cnt.numpy(),
+                                  K, alpha)
+        return VemBound(torch.from_numpy(doc), torch.from_numpy(tot))
+    if doc_pair_ptr is None:
+        doc_pair_ptr = torch.searchsorted(pair_doc, torch.arange(D + 1, dtype=torch.int32, device=dev)).to(torch.int64)
+    doc = torch.empty(D, dtype=torch.float64, device=dev)
+    tot = torch.empty(2, dtype=torch.float64, device=dev)
+    # x [D, KS], T and A [D], a head and a tail record per wave of 64 pairs, two partials per tile
+    # of 256 documents: never initialised
+    n = D * KS + 2 * D + 2 * ((P + 63) // 64) + 2 * ((D + 255) // 256)
+    scratch = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().oni_vem_bound(_lib.ptr(gamma) if D else None, _lib.ptr(table), int(table.shape[0]), KS, K,
+                                        _lib.ptr(pair_doc) if P else None, _lib.ptr(pair_word) if P else None,
+                                        _lib.ptr(pair_cnt) if P else None, _lib.ptr(doc_pair_ptr) if D else None, P, D,
+                                        alpha, _lib.ptr(doc) if D else None, _lib.ptr(tot), _lib.ptr(scratch),
+                                        int(scratch.numel()), int(grid or 0), _lib.stream()), "oni_vem_bound")
+    return VemBound(doc, tot)

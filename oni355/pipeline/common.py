@@ -546,13 +546,15 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                     chunk_len: int, comm: Comm | None, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None,
                     train: bool = True, timer: StageTimer | None = None, ldac_dir: str | None = None,
                     ldac_lag: int = 0, word_ids: torch.Tensor | None = None, n_event0: int = 0,
-                    on_train=None, method: str = "gibbs", em_iters: int = 30, var_iters: int = 20) -> LdaRun:
+                    on_train=None, method: str = "gibbs", em_iters: int = 30, var_iters: int = 20,
+                    em_tol: float = 0.0, estimate_alpha: bool = False) -> LdaRun:
     """Token keys → owner routing → local corpus → Gibbs LDA trained for ``sweeps`` sweeps.
 
     ``method`` ``"vem"`` trains the model by variational EM instead (models.vem_gpu.VarLDA:
     ``em_iters`` EM iterations of ``var_iters`` E-step iterations each, single GPU, no seed):
     ``sweeps``, ``seed``, ``burnin``, ONI_CHAINS, checkpoints, LAG snapshots and the MH burn-in
-    do not apply.
+    do not apply. ``em_tol`` > 0 makes ``em_iters`` a maximum (EM stops on the variational bound's
+    relative change), ``estimate_alpha`` re-estimates α every EM iteration (``VarLDA.run``).
 
     ``word_ids`` (int32, from :func:`encode_words`) skips the vocabulary lookup of ``word_keys64``.
     Where :func:`fused_corpus` holds, ``doc_keys64`` may also be int32 u32 bits or the two int32
@@ -634,7 +636,7 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
         dcorpus = corpus_for(Gd) if Gd != G else None
     if method == "vem":
         return _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every,
-                          train, timer, log, on_train)
+                          train, timer, log, on_train, em_tol, estimate_alpha)
     # ONI_CHAINS = C > 1: C independent chains of sweeps // C sweeps each (same total sweep count),
     # scored by the average of their pair scores (LdaRun.pair_scores): the top-N then depends less
     # on any one chain's seed. Dense samplers only, no checkpointing.
@@ -721,28 +723,41 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
     return run
 
 
-def check_train_method(method: str, em_iters: int, var_iters: int, comm=None, ckpt=None, ldac_dir=None) -> None:
+def check_train_method(method: str, em_iters: int, var_iters: int, comm=None, ckpt=None, ldac_dir=None,
+                       em_tol: float = 0.0, estimate_alpha: bool = False) -> None:
     """``method`` of run_* : ``"gibbs"`` or ``"vem"``; what vem training does not combine with."""
     if method not in ("gibbs", "vem"):
         raise ValueError(f"method must be 'gibbs' or 'vem', not {method!r}")
+    if method != "vem" and (em_tol or estimate_alpha):
+        raise ValueError("em_tol and estimate_alpha belong to method='vem'")
     if method == "vem":
         if int(em_iters) < 0 or int(var_iters) < 0:
             raise ValueError("em_iters and var_iters must be ≥ 0")
+        if not float(em_tol) >= 0:
+            raise ValueError("em_tol must be ≥ 0")
         if comm is not None and comm.dist:
             raise NotImplementedError("vem training is single-GPU")
         if ckpt is not None or ldac_dir:
             raise ValueError("vem training writes no checkpoints and no lda-c snapshots")
 
 
-def vem_stats(method: str, em_iters: int, var_iters: int) -> dict:
-    """What ``stats`` gains in vem mode (nothing with the Gibbs sampler)."""
+def vem_stats(method: str, em_iters: int, var_iters: int, em_tol: float = 0.0, estimate_alpha: bool = False,
+              run=None) -> dict:
+    """What ``stats`` gains in vem mode (nothing with the Gibbs sampler). With ``em_tol`` > 0 or
+    ``estimate_alpha`` also what the trained ``run`` (LdaRun) ended with: the variational bound of
+    its final E-step, the final α, the EM iterations run and whether the exit was the tolerance."""
     if method != "vem":
         return {}
-    return {"train_method": "vem", "em_iters": int(em_iters), "var_iters": int(var_iters)}
+    out = {"train_method": "vem", "em_iters": int(em_iters), "var_iters": int(var_iters)}
+    if (em_tol > 0 or estimate_alpha) and run is not None:
+        m, elbo = run.model, run.model.bound()
+        out.update(elbo=elbo, elbo_per_token=elbo / max(int(run.corpus.T), 1), alpha_final=float(m.alpha),
+                   em_iters_done=int(m.sweeps_done), em_converged=bool(m.converged))
+    return out
 
 
 def _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every, train,
-               timer, log, on_train) -> LdaRun:
+               timer, log, on_train, em_tol=0.0, estimate_alpha=False) -> LdaRun:
     """The ``init`` / ``train`` stages of :func:`build_and_train` with ``method="vem"``."""
     from ..models.vem_gpu import VarLDA
     with timer.stage("init"):
@@ -753,7 +768,7 @@ def _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters
     with timer.stage("train"):
         if on_train is not None:
             on_train()
-        model.run(em_iters, var_iters, eval_every=eval_every, log=log)
+        model.run(em_iters, var_iters, eval_every=eval_every, log=log, em_tol=em_tol, estimate_alpha=estimate_alpha)
     model.close()
     if not model.likelihoods or model.likelihoods[-1][0] != model.sweeps_done:
         model.record_likelihood()
@@ -1097,9 +1112,9 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
                           feedback=None, row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None,
                           timer: StageTimer | None = None, ldac_dir: str | None = None,
                           ldac_lag: int = 0, key_bits: int = 64, method: str = "gibbs", em_iters: int = 30,
-                          var_iters: int = 20) -> SingleResult:
+                          var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False) -> SingleResult:
     """Shared DNS/proxy path: one (doc, word) token per event; score = θ_doc·φ_word (C24)."""
-    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir)
+    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha)
     dev = doc_keys64.device
     timer = timer or StageTimer(dev)
     with timer.stage("vocab"):
@@ -1115,7 +1130,8 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     n = int(doc_keys64.numel())
     run = build_and_train(dk, None, wts, vocab, K, alpha, beta, seed, sweeps, chunk_len, comm, eval_every=eval_every, burnin=burnin,
                           ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag, word_ids=wids,
-                          n_event0=n, method=method, em_iters=em_iters, var_iters=var_iters)
+                          n_event0=n, method=method, em_iters=em_iters, var_iters=var_iters, em_tol=em_tol,
+                          estimate_alpha=estimate_alpha)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     if run.route is not None:
         with timer.stage("score_prep"):
@@ -1142,7 +1158,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     stats = run.corpus.stats()
     stats.update({"events": int(doc_keys64.numel()),
                   "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
-    stats.update(vem_stats(method, em_iters, var_iters))
+    stats.update(vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run))
     return SingleResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(),
                         words=words.cpu().numpy().view(np.uint64), timings=t, stats=stats, lda=run)
 

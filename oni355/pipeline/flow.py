@@ -226,15 +226,19 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
              device="cpu", comm: Comm | None = None, feedback: dict | None = None, dupfactor: int = 1000,
              row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None, ldac_dir: str | None = None,
              ldac_lag: int = 0, device_cols: dict | None = None, on_train=None, method: str = "gibbs",
-             em_iters: int = 30, var_iters: int = 20) -> FlowResult:
+             em_iters: int = 30, var_iters: int = 20, em_tol: float = 0.0,
+             estimate_alpha: bool = False) -> FlowResult:
     """Full suspicious-connects for one (rank-local shard of a) day of flows. ``device_cols``:
     the day's :data:`DEVICE_COLS` already on the device (e.g. from io.staging.Prefetcher, which
     uploaded them while the previous day computed); ``cols`` still supplies the host rows.
     ``on_train``: see :func:`common.build_and_train`. ``method`` ``"vem"``: the model is trained by
     ``em_iters`` iterations of variational EM (``var_iters`` E-step iterations each) instead of the
     Gibbs sampler: single GPU, no seed (``sweeps`` and ``seed`` are ignored), ``stats`` carries
-    ``train_method``, ``em_iters`` and ``var_iters``."""
-    common.check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir)
+    ``train_method``, ``em_iters`` and ``var_iters``. ``em_tol`` > 0 stops EM once the variational
+    bound's relative change is in [0, em_tol] (``em_iters`` is then the maximum); ``estimate_alpha``
+    re-estimates α every EM iteration. With either, ``stats`` also carries ``elbo``,
+    ``elbo_per_token``, ``alpha_final``, ``em_iters_done`` and ``em_converged``."""
+    common.check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha)
     timer = StageTimer(device)
     if device_cols is None:
         cols, feedback = with_ipv6_keys(cols, comm, (feedback,)) if feedback else (with_ipv6_keys(cols, comm), None)
@@ -271,7 +275,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
     run = common.build_and_train(doc_keys, None, weights, vocab, K, alpha, beta, seed, sweeps, chunk_len, comm,
                                  eval_every=eval_every, burnin=burnin, ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir,
                                  ldac_lag=ldac_lag, word_ids=wids, n_event0=n, on_train=on_train, method=method,
-                                 em_iters=em_iters, var_iters=var_iters)
+                                 em_iters=em_iters, var_iters=var_iters, em_tol=em_tol, estimate_alpha=estimate_alpha)
 
     # ---- scoring --------------------------------------------------------------------------------
     hist = torch.zeros(2048, dtype=torch.int32, device=d["sip"].device)
@@ -327,7 +331,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
         wparts = allp[:, 3:5].to(torch.int32)
     stats = run.corpus.stats()
     stats.update({"n_flows": n, "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
-    stats.update(common.vem_stats(method, em_iters, var_iters))
+    stats.update(common.vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run))
     return FlowResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), src_scores=parts[:, 0].cpu().numpy(),
                       dst_scores=parts[:, 1].cpu().numpy(), src_words=wparts[:, 0].cpu().numpy().view(np.uint32),
                       dst_words=wparts[:, 1].cpu().numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats,

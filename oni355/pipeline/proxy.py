@@ -228,10 +228,10 @@ def run_proxy(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxr
               dupfactor: int = 1000, row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None,
               log=None, ldac_dir: str | None = None, ldac_lag: int = 0,
               device_cols: dict | None = None, method: str = "gibbs", em_iters: int = 30,
-            var_iters: int = 20) -> common.SingleResult:
+            var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False) -> common.SingleResult:
     """``device_cols``: :func:`host_arrays` already on the device (e.g. prefetched by
     io.staging.Prefetcher while the previous day computed). ``method`` / ``em_iters`` /
-    ``var_iters``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
+    ``var_iters`` / ``em_tol`` / ``estimate_alpha``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
     timer = StageTimer(device)
     with timer.stage("h2d"):
         d = dict(device_cols) if device_cols is not None else \
@@ -248,7 +248,8 @@ def run_proxy(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxr
     res = common.run_single_doc_events(docs, words, K, sweeps, tol, maxresults, alpha, beta, seed, chunk_len, comm,
                                        feedback=fb, row_offset=row_offset, eval_every=eval_every, burnin=burnin, ckpt=ckpt, log=log,
                                        timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag,
-                                       key_bits=34, method=method, em_iters=em_iters, var_iters=var_iters)
+                                       key_bits=34, method=method, em_iters=em_iters, var_iters=var_iters,
+                                       em_tol=em_tol, estimate_alpha=estimate_alpha)
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in cuts.items()}
     res.stats["ua_table"] = ua_table
     return res

@@ -1,7 +1,8 @@
 """Specification of variational-EM training on the device (csrc/kernels/vem.hip, ops.vem_resp /
 vem_wsum / vem_table, models.vem_gpu.VarLDA): smoothed (MAP) variational EM with fixed α and β over
-the corpus' distinct (doc, word, count) pairs ``(d_p, w_p, c_p)``, lda-c's ``lda est`` without its
-α estimation, its ELBO and its convergence exits. No seed anywhere::
+the corpus' distinct (doc, word, count) pairs ``(d_p, w_p, c_p)``: lda-c's ``lda est``. Its variational
+bound, its EM convergence exit and its α estimation are options (:func:`bound`, :func:`alpha_newton`,
+``em_tol`` / ``estimate_alpha`` of :func:`vem`), off by default. No seed anywhere::
 
     init      ss0[w,k] = 1/V + u(w,k)        u = top 24 bits of mix32(w·K + k) · 2^-24
               table    = table(ss0)
@@ -17,14 +18,24 @@ the corpus' distinct (doc, word, count) pairs ``(d_p, w_p, c_p)``, lda-c's ``lda
               columns K .. KS−1 are zero
     θ = vfold(pairs, table, ...)                          one final E-step against the final table
 
-Both iteration counts are fixed: no result depends on a threshold. Scoring the training day against
-the saved table with the variational fold-in (``var_iters`` iterations, no prior) therefore
-reproduces θ. The likelihood reported is the plug-in one of :func:`oni355.ref.fit_spec.doc_fit`.
+``var_iters`` is fixed, and so is ``em_iters`` unless ``em_tol`` > 0. Scoring the training day against
+the saved table with the variational fold-in (``var_iters`` iterations, no prior, the saved α)
+therefore reproduces θ. The likelihood reported is the plug-in one of
+:func:`oni355.ref.fit_spec.doc_fit`; the bound EM climbs is :func:`bound`::
+
+    S_d = Σ_{k<K} γ_dk      E_dk = ψ(γ_dk) − ψ(S_d)      x_dk = exp(E_dk)
+    A_d = Σ_{k<K} ψ(γ_dk) − K·ψ(S_d)                                 (α statistic of the document)
+    T_d = lgamma(Kα) − K·lgamma(α) − lgamma(S_d) + Σ_{k<K} [(α − γ_dk)·E_dk + lgamma(γ_dk)]
+    L_d = T_d + Σ_{p in d} c_p · log(Σ_{k<K} table[w_p,k] · x_{d_p,k})
+
+(the pair term is lda-c's Σ_k φ_pk(E_k − log φ_pk + log β_kw) at the optimal φ, where it is log s_p).
 
 Everything is vectorised NumPy on ``dtype``: float64 is the reference, float32 shows what f32
 arithmetic alone costs.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -128,22 +139,101 @@ def loglik(theta, tab, pair_doc, pair_word, pair_cnt, V: int) -> float:
                                   th.shape[0], int(V))[4][0])
 
 
+def bound(gamma, tab, pair_doc, pair_word, pair_cnt, K: int, alpha: float):
+    """(L_d float64 [D], float64 [2] = Σ_d L_d, Σ_d A_d): the variational bound per document and the α
+    sufficient statistic, in float64 from γ [D, KS] and the table as given (see the module text).
+    A pair whose s_p is 0 gives −inf; pairs naming a document outside [0, D) or a word outside the
+    table's rows contribute nothing."""
+    g = np.asarray(gamma).astype(np.float64)[:, : int(K)]
+    tab = np.asarray(tab)
+    D, K, alpha = g.shape[0], int(K), float(alpha)
+    pd = np.asarray(pair_doc).astype(np.int64)
+    pw = np.asarray(pair_word).astype(np.int64)
+    ok = (pd >= 0) & (pd < D) & (pw >= 0) & (pw < tab.shape[0])
+    pd, pw, c = pd[ok], pw[ok], np.asarray(pair_cnt).astype(np.float64)[ok]
+    S = g.sum(1)
+    psi = torch.digamma(torch.from_numpy(np.ascontiguousarray(g))).numpy()
+    pS = torch.digamma(torch.from_numpy(S)).numpy()
+    lg = torch.lgamma(torch.from_numpy(np.ascontiguousarray(g))).numpy()
+    E = psi - pS[:, None]
+    A = psi.sum(1) - K * pS
+    L = (math.lgamma(K * alpha) - K * math.lgamma(alpha)) - torch.lgamma(torch.from_numpy(S)).numpy() \
+        + ((alpha - g) * E + lg).sum(1)
+    s = (tab[pw, :K].astype(np.float64) * np.exp(E)[pd]).sum(1)
+    with np.errstate(divide="ignore"):
+        np.add.at(L, pd, c * np.log(s))
+    return L, np.array([L.sum(), A.sum()], np.float64)
+
+
+def _f64(fn, x: float) -> float:
+    return float(fn(torch.tensor(float(x), dtype=torch.float64)))
+
+
+def alpha_newton(alpha_ss: float, D: int, K: int) -> float:
+    """The symmetric α that maximises the bound given Σ_d A_d: lda-c's Newton iteration on log α
+    from 100 (``mle`` of csrc/lda_cpu/lda_vem.cpp), float64, at most 1000 steps, until |df| ≤ 1e-5,
+    with its ×10 restart when a step leaves the representable range."""
+    D, K, ss = float(D), float(K), float(alpha_ss)
+    init_a = 100.0
+    log_a, df = math.log(init_a), 1.0
+    for _ in range(1000):
+        if abs(df) <= 1e-5:
+            break
+        try:
+            a = math.exp(log_a)
+        except OverflowError:
+            a = float("nan")
+        if math.isnan(a) or math.isinf(a) or a <= 0.0:
+            init_a *= 10.0
+            a = init_a
+            log_a = math.log(a)
+        df = D * (K * _f64(torch.digamma, K * a) - K * _f64(torch.digamma, a)) + ss
+        d2f = D * (K * K * _f64(lambda t: torch.polygamma(1, t), K * a) - K * _f64(lambda t: torch.polygamma(1, t), a))
+        log_a -= df / (d2f * a + df)
+    return math.exp(log_a)
+
+
 def vem(pair_doc, pair_word, pair_cnt, doc_pair_ptr, V: int, K: int, KS: int, alpha: float, beta: float,
-        em_iters: int, var_iters: int, dtype=np.float64, trace=None):
+        em_iters: int, var_iters: int, dtype=np.float64, trace=None, em_tol: float = 0.0,
+        estimate_alpha: bool = False, bounds=None):
     """(θ [D, KS], table [V + 1, KS], ss_k [KS]) after ``em_iters`` EM iterations and the final
     E-step. ``trace``: a list that receives (iteration, plug-in log-likelihood) before every
-    iteration's M-step and after the last E-step."""
+    iteration's M-step and after the last E-step.
+
+    With ``em_tol`` > 0 or ``estimate_alpha`` every iteration's E-step is followed by :func:`bound`
+    (float64, from the ``dtype`` γ and table, as the device computes it from f32 ones) and
+    ``bounds`` (a list) receives (iteration, L, conv, α) with conv = (L_old − L)/L_old, 1.0 for the
+    first, then (iterations run, L of the final E-step, None, final α). ``estimate_alpha``: after
+    the table update α ← :func:`alpha_newton` rounded to float32 (what a saved model carries).
+    ``em_tol`` > 0: ``em_iters`` is the maximum; EM stops after the M-step of an iteration that
+    is at least the third and has 0 ≤ conv ≤ em_tol."""
     wm_ptr, wm_doc, _, wm_pos = word_major(pair_word, pair_doc, V)
     tab, ssk = table(init_ss(V, K, KS, dtype), K, beta, dtype)
+    track = em_tol > 0 or estimate_alpha
+    L_old, done = 0.0, 0
     for it in range(int(em_iters)):
         theta, g = vfold_spec.vfold(pair_word, pair_cnt, doc_pair_ptr, tab, K, alpha, None, var_iters, dtype)
         if trace is not None:
             trace.append((it, loglik(theta, tab, pair_doc, pair_word, pair_cnt, V)))
+        conv = 1.0
+        if track:
+            _, (L, a_ss) = bound(g, tab, pair_doc, pair_word, pair_cnt, K, alpha)
+            conv = 1.0 if L_old == 0 else (L_old - L) / L_old
+            L_old = L
+            if bounds is not None:
+                bounds.append((it, float(L), float(conv), float(alpha)))
         e, q = resp(g, tab, pair_doc, pair_word, pair_cnt, K, dtype)
         q_wm = np.empty_like(q)
         q_wm[wm_pos] = q
         tab, ssk = table(wsum(e, q_wm, tab, wm_ptr, wm_doc, K, dtype), K, beta, dtype)
-    theta, _ = vfold_spec.vfold(pair_word, pair_cnt, doc_pair_ptr, tab, K, alpha, None, var_iters, dtype)
+        if estimate_alpha:
+            alpha = float(np.float32(alpha_newton(a_ss, g.shape[0], K)))
+        done = it + 1
+        if em_tol > 0 and done >= 3 and 0 <= conv <= em_tol:
+            break
+    theta, g = vfold_spec.vfold(pair_word, pair_cnt, doc_pair_ptr, tab, K, alpha, None, var_iters, dtype)
     if trace is not None:
-        trace.append((int(em_iters), loglik(theta, tab, pair_doc, pair_word, pair_cnt, V)))
+        trace.append((done if track else int(em_iters), loglik(theta, tab, pair_doc, pair_word, pair_cnt, V)))
+    if track and bounds is not None:
+        bounds.append((done, float(bound(g, tab, pair_doc, pair_word, pair_cnt, K, alpha)[1][0]), None, float(alpha)))
     return theta, tab, ssk
