@@ -23,6 +23,16 @@ the overlap of its top-N with the fixed day's and the planted recall; the α tra
 timed alone with device events next to ops.doc_fit on the same pairs.
 
   python bench/vem_day.py --em-tol 1e-4 --out profiles/vem/bound_flow_12.5M_k20.json
+
+``--var-tol X[,Y…]`` runs a third comparison (no Gibbs days): the fixed day and, per tolerance, the day
+with ``var_tol`` alone and with ``var_tol`` + ``warm_start``, alternating in one process; per variant
+ms per day and per EM iteration, the ``var_iters_trace``, the final bound, the overlap of its top-N
+with the fixed day's and the planted recall. Then, with device events on the fixed day's final table:
+ops.vfold against ops.vfold_exit(tol=0) (what the exit machinery costs), the E-step with each
+tolerance from the cold start and from the previous γ, and what the lockstep of a round costs
+(Σ n_it against Σ over rounds of documents × the round's largest n_it).
+
+  python bench/vem_day.py --var-tol 1e-3,1e-5 --out profiles/vem/exit_flow_12.5M_k20.json
 """
 from __future__ import annotations
 
@@ -138,6 +148,97 @@ def bound_ab(a, run, day, kw: dict, planted: set, dev) -> int:
     return 0
 
 
+def lockstep(n_it, ptr) -> dict:
+    """Updates the documents of the rounds needed against updates the rounds ran in lockstep: a wave
+    owns 16 consecutive documents and packs them, in order, into rounds of at most 64 pairs
+    (k_vfold_exit); a document over 64 pairs is the block path's and waits for nobody."""
+    import numpy as np
+    size = np.diff(ptr)
+    need = ran = nbig = 0
+    for w0 in range(0, size.size, 16):
+        docs, used, top = 0, 0, 0
+        for d in range(w0, min(w0 + 16, size.size)):
+            if size[d] > 64:
+                nbig += 1
+                continue
+            if docs and used + size[d] > 64:
+                ran += docs * top
+                docs, used, top = 0, 0, 0
+            docs, used, top = docs + 1, used + int(size[d]), max(top, int(n_it[d]))
+            need += int(n_it[d])
+        ran += docs * top
+    return {"updates_needed": need, "updates_in_lockstep": ran, "ratio": round(ran / max(need, 1), 4), "block_path_docs": nbig}
+
+
+def exit_ab(a, run, day, kw: dict, planted: set, dev) -> int:
+    """The ``--var-tol`` comparison of the module text."""
+    import torch
+
+    from oni355 import ops
+    tols = [float(x) for x in a.var_tol.split(",")]
+    base = dict(method="vem", em_iters=a.em_iters, var_iters=a.var_iters, **kw)
+    variants = {"fixed": {}}
+    for x in tols:
+        variants[f"tol{x:g}"] = dict(var_tol=x)
+        variants[f"tol{x:g}_warm"] = dict(var_tol=x, warm_start=True)
+    for v in variants.values():  # one untimed day each
+        run(day.cols, **v, **base)
+    days = {n: [] for n in variants}
+    tops, models = {}, {}
+    for r in range(a.rounds):
+        for name, v in variants.items():
+            torch.cuda.synchronize(dev)
+            ts = time.perf_counter()
+            res = run(day.cols, **v, **base)
+            torch.cuda.synchronize(dev)
+            wall = time.perf_counter() - ts
+            m, rows = res.lda.model, set(res.rows.tolist())
+            train_ms = res.timings.get("train_dev_s", res.timings.get("train_s", 0.0)) * 1e3
+            line = {"variant": name, "round": r, "day_ms": round(wall * 1e3, 2), "train_ms": round(train_ms, 3),
+                    "ms_per_em_iter": round(train_ms / max(a.em_iters, 1), 4), "bound": m.bound(),
+                    "loglik": res.stats["loglik"], "var_iters_trace": [round(x, 3) for x in m.var_iters_trace],
+                    "planted_recall_topN": round(len(rows & planted) / max(len(planted), 1), 4)}
+            days[name].append(line)
+            tops[name], models[name] = rows, m
+            print(json.dumps(line), flush=True)
+            del res
+    n_top = max(len(tops["fixed"]), 1)
+
+    def med(v, key):
+        return statistics.median(x[key] for x in v)
+    summary = {n: {"day_ms_median": med(v, "day_ms"),
+                   "day_ms_spread": round(max(x["day_ms"] for x in v) - min(x["day_ms"] for x in v), 2),
+                   "ms_per_em_iter_median": med(v, "ms_per_em_iter"), "bound": v[-1]["bound"],
+                   "var_iters_trace": v[-1]["var_iters_trace"], "planted_recall_topN": v[-1]["planted_recall_topN"],
+                   "top_overlap_with_fixed": round(len(tops[n] & tops["fixed"]) / n_top, 4)} for n, v in days.items()}
+    m = models["fixed"]
+    pw, pc, ptr = m._pairs
+    args = (pw, pc, ptr, m.table, m.K, m.alpha, None, m.var_iters)
+    # the warm start's best case: the E-step restarted from its own fixed-count γ against the same table
+    # (an EM that has converged); the days' var_iters_trace has what the real iterations needed
+    _, g_prev = ops.vfold(*args, want_gamma=True)
+    ops_ms = {"vfold": _timed(lambda: ops.vfold(*args, want_gamma=True), a.op_reps),
+              "vfold_exit_tol0": _timed(lambda: ops.vfold_exit(*args, 0.0), a.op_reps)}
+    lock = {}
+    for x in tols:
+        ops_ms[f"vfold_exit_tol{x:g}_cold"] = _timed(lambda: ops.vfold_exit(*args, x), a.op_reps)
+        ops_ms[f"vfold_exit_tol{x:g}_from_converged"] = _timed(lambda: ops.vfold_exit(*args, x, g_prev), a.op_reps)
+        n_cold = ops.vfold_exit(*args, x)[2].cpu().numpy()
+        n_warm = ops.vfold_exit(*args, x, g_prev)[2].cpu().numpy()
+        hp = ptr.cpu().numpy()
+        lock[f"tol{x:g}_cold"] = dict(lockstep(n_cold, hp), n_it_mean=round(float(n_cold.mean()), 3))
+        lock[f"tol{x:g}_from_converged"] = dict(lockstep(n_warm, hp), n_it_mean=round(float(n_warm.mean()), 3))
+    out = {"source": a.source, "flows": a.flows, "topics": a.topics, "em_iters": a.em_iters, "var_iters": a.var_iters,
+           "var_tol": tols, "rounds": a.rounds, "pairs": int(pw.numel()), "docs": int(m.c.D), "summary": summary,
+           "ops_ms": ops_ms, "lockstep": lock, "days": days}
+    print(json.dumps({"summary": summary, "ops_ms": ops_ms, "lockstep": lock}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--flows", type=int, default=12_500_000)
@@ -154,6 +255,7 @@ def main() -> int:
     ap.add_argument("--source", choices=["flow", "dns"], default="flow")
     ap.add_argument("--em-tol", type=float, default=0.0, help="> 0: the convergence-exit / α comparison instead")
     ap.add_argument("--em-max", type=int, default=100, help="--em-tol: the most EM iterations of the tol variant")
+    ap.add_argument("--var-tol", default="", help="X[,Y…]: the per-document exit / warm start comparison instead")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -176,6 +278,8 @@ def main() -> int:
     print(f"generated {a.flows} {a.source} events in {time.perf_counter() - t0:.1f} s", flush=True)
     if a.em_tol > 0:
         return bound_ab(a, run, day, kw, planted, dev)
+    if a.var_tol:
+        return exit_ab(a, run, day, kw, planted, dev)
     vkw = dict(method="vem", em_iters=a.em_iters, var_iters=a.var_iters)
     variants = {"gibbs": lambda r: run(day.cols, sweeps=a.sweeps, seed=101 + r, **kw),
                 "vem": lambda r: run(day.cols, **vkw, **kw)}

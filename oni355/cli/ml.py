@@ -65,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "or vb (deterministic variational fold-in: no seed, --infer-sweeps/--infer-avg-last unused)")
     ap.add_argument("--infer-iters", type=int, default=None, metavar="N",
                     help="--model --infer-method vb: fixed-point iterations (default 20, lda-c's var max iter)")
+    ap.add_argument("--infer-tol", type=float, default=None, metavar="X",
+                    help="--model --infer-method vb: stop an IP's iterations once the relative change of its "
+                         "variational parameters is ≤ X (--infer-iters is then the maximum; default: run them all)")
     ap.add_argument("--infer-fit", action="store_true",
                     help="--model: also report how well the model fits the batch: the batch log-likelihood and "
                          "perplexity in metrics.jsonl, and <source>_fit.csv with the MAXRESULTS worst-fitting IPs")
@@ -82,6 +85,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--em-tol", type=float, default=None, metavar="X",
                     help="--train-method vem: stop EM once the variational bound's relative change is in [0, X] "
                          "(at least three iterations; --em-iters is then the maximum; default: run them all)")
+    ap.add_argument("--var-tol", type=float, default=None, metavar="X",
+                    help="--train-method vem: stop an IP's E-step once the relative change of its variational "
+                         "parameters is ≤ X (lda-c's 'var converged' as a gamma-change rule; --var-iters is then "
+                         "the maximum; score the saved model with --infer-tol X to reproduce the day's topic mixes)")
+    ap.add_argument("--warm-start", action="store_true",
+                    help="--train-method vem: start every EM iteration's E-step from the previous iteration's "
+                         "variational parameters (the final E-step still starts cold)")
     ap.add_argument("--estimate-alpha", action="store_true",
                     help="--train-method vem: re-estimate the symmetric alpha every EM iteration (lda-c's "
                          "'alpha estimate'); the saved model carries the estimate")
@@ -273,7 +283,8 @@ def main(argv=None) -> int:
         if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit(f"oni-ml: {opt} is single-GPU (fold-in scoring and model saving run on one GPU); drop --gpus")
     for flag, val in (("--em-iters", a.em_iters), ("--var-iters", a.var_iters), ("--em-tol", a.em_tol),
-                      ("--estimate-alpha", a.estimate_alpha or None)):
+                      ("--estimate-alpha", a.estimate_alpha or None), ("--var-tol", a.var_tol),
+                      ("--warm-start", a.warm_start or None)):
         if val is not None and a.train_method != "vem":
             raise SystemExit(f"oni-ml: {flag} belongs to variational EM; it needs --train-method vem")
         if val is not None and val < 0:
@@ -289,12 +300,16 @@ def main(argv=None) -> int:
             raise SystemExit("oni-ml: --train-method vem does not combine with --max-restarts (no checkpoints)")
     if a.infer_fit and not a.model:
         raise SystemExit("oni-ml: --infer-fit reports the fit of a saved model; it needs --model FILE")
-    for flag, val in (("--infer-method", a.infer_method), ("--infer-iters", a.infer_iters)):
+    for flag, val in (("--infer-method", a.infer_method), ("--infer-iters", a.infer_iters), ("--infer-tol", a.infer_tol)):
         if val is not None and not a.model:
             raise SystemExit(f"oni-ml: {flag} chooses how a saved model's day is folded in; it needs --model FILE")
     if a.model:
         if a.infer_iters is not None and a.infer_iters < 0:
             raise SystemExit("oni-ml: --infer-iters must be ≥ 0")
+        if a.infer_tol is not None and not 0 <= a.infer_tol < float("inf"):
+            raise SystemExit("oni-ml: --infer-tol must be finite and ≥ 0")
+        if a.infer_tol is not None and a.infer_method != "vb":
+            raise SystemExit("oni-ml: --infer-tol belongs to the variational fold-in; it needs --infer-method vb")
         for flag, val in (("--ckpt-dir", a.ckpt_dir), ("--ldac-out", a.ldac_out), ("--save-model", a.save_model)):
             if val:
                 raise SystemExit(f"oni-ml: --model scores against a saved model and trains nothing; {flag} does not apply")
@@ -366,7 +381,7 @@ def main(argv=None) -> int:
     if a.train_method == "vem":
         common_kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
                          var_iters=20 if a.var_iters is None else a.var_iters, em_tol=a.em_tol or 0.0,
-                         estimate_alpha=a.estimate_alpha)
+                         estimate_alpha=a.estimate_alpha, var_tol=a.var_tol or 0.0, warm_start=a.warm_start)
     if a.ldac_out and a.ldac_lag > 0:
         common_kw.update(ldac_dir=os.path.join(a.ldac_out, f"rank{rank}") if world > 1 else a.ldac_out,
                          ldac_lag=a.ldac_lag)
@@ -380,7 +395,8 @@ def main(argv=None) -> int:
         score_kw = dict(tol=cfg.TOL, maxresults=cfg.MAXRESULTS, sweeps=a.infer_sweeps, avg_last=a.infer_avg_last,
                         seed=cfg.SEED, device=device, comm=comm, feedback=fb, chunk_len=cfg.CHUNK_LEN,
                         row_offset=row_off, log=log, prior_mass=a.infer_prior_mass, fit=a.infer_fit,
-                        method=a.infer_method or "gibbs", iters=20 if a.infer_iters is None else a.infer_iters)
+                        method=a.infer_method or "gibbs", iters=20 if a.infer_iters is None else a.infer_iters,
+                        infer_tol=a.infer_tol or 0.0)
         if a.source == "flow":
             from ..pipeline.flow import score_flow
             res = score_flow(cols, model, **score_kw)
@@ -466,7 +482,7 @@ def _main_days(a, cfg, comm, device, dates: list[str], log) -> int:
     if a.train_method == "vem":
         kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
                   var_iters=20 if a.var_iters is None else a.var_iters, em_tol=a.em_tol or 0.0,
-                  estimate_alpha=a.estimate_alpha)
+                  estimate_alpha=a.estimate_alpha, var_tol=a.var_tol or 0.0, warm_start=a.warm_start)
     if a.source == "dns":
         kw.update(top_domains=top, user_domain=cfg.USER_DOMAIN)
     elif a.source == "proxy":

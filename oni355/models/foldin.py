@@ -122,7 +122,7 @@ class FoldIn:
 class VarFoldIn:
     """Variational (mean-field) fold-in over ``corpus``' distinct (doc, word) pairs: the
     deterministic, seed-free counterpart of :class:`FoldIn` (ops.vfold, one launch for every
-    iteration of every document). Same inputs as FoldIn without ``seed`` / ``fuse``; it holds no
+    iteration of every document; with a tolerance ops.vfold_exit, which stops each document on its own). Same inputs as FoldIn without ``seed`` / ``fuse``; it holds no
     topic assignments and no count rows."""
 
     def __init__(self, corpus: Corpus, table: torch.Tensor, K: int, alpha: float, prior: torch.Tensor | None = None):
@@ -144,17 +144,28 @@ class VarFoldIn:
             prior = prior[:c.D].contiguous()
         self.prior = prior
         self._theta = None
+        self._n_it = None  # updates per document, when run with a tolerance
         self.iters_done = 0
         self.launches = {"vfold": 0}
 
     @traced("oni:vfold.run")
-    def run(self, iters: int = 20) -> "VarFoldIn":
+    def run(self, iters: int = 20, tol: float = 0.0) -> "VarFoldIn":
+        """``tol`` > 0: a document stops once Σ|γ_new − γ_old| ≤ tol · Σγ (``iters`` is the maximum)."""
         c = self.c
-        self._theta = ops.vfold(c.pair_word.contiguous(), c.pair_cnt.contiguous(), c.doc_pair_ptr.contiguous(),
-                                self.table, self.K, self.alpha, self.prior, iters)
+        pairs = (c.pair_word.contiguous(), c.pair_cnt.contiguous(), c.doc_pair_ptr.contiguous())
+        if tol > 0:
+            self._theta, _, self._n_it = ops.vfold_exit(*pairs, self.table, self.K, self.alpha, self.prior, iters, tol)
+        else:
+            self._theta, self._n_it = ops.vfold(*pairs, self.table, self.K, self.alpha, self.prior, iters), None
         self.launches = {"vfold": 1}
         self.iters_done = int(iters)
         return self
+
+    def iters_mean(self) -> float:
+        """Mean updates per document of the last run (``iters`` itself without a tolerance)."""
+        if self._n_it is None or not self._n_it.numel():
+            return float(self.iters_done)
+        return float(self._n_it.sum()) / int(self._n_it.numel())
 
     def theta(self) -> torch.Tensor:
         """θ f32 [D, KS], zero past K."""

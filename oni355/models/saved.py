@@ -164,7 +164,8 @@ class SavedModel:
         if hasattr(m, "phi_oov"):  # variational EM (models.vem_gpu.VarLDA): no seed, its own unseen-word row
             prv = {"train_method": "vem", "em_iters": int(m.sweeps_done), "var_iters": int(m.var_iters),
                    "tree_hash": prov.tree_hash("hip"), "em_tol": float(m.em_tol),
-                   "estimate_alpha": bool(m.estimate_alpha)}
+                   "estimate_alpha": bool(m.estimate_alpha), "var_tol": float(m.var_tol),
+                   "warm_start": bool(m.warm_start)}
             if m.em_tol > 0 or m.estimate_alpha:
                 prv["elbo"] = m.bound()  # the variational bound of the final E-step
             phi_oov = m.phi_oov().cpu().numpy()

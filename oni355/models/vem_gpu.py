@@ -14,7 +14,13 @@ variational bound lda-c writes to likelihood.dat, and the α sufficient statisti
 totals back: ``em_tol`` stops EM on the bound's relative change, ``estimate_alpha`` re-estimates
 the symmetric α by lda-c's Newton step after every table update.
 
-Not done here: warm-starting γ between EM iterations, a per-document E-step exit, vector α.
+Two more, also off by default, move the E-step to ``ops.vfold_exit``: ``var_tol`` > 0 stops a
+document's E-step once Σ|γ_new − γ_old| ≤ var_tol · Σγ (lda-c's ``var converged``, as a γ-change
+rule, not lda-c's likelihood-change rule), ``warm_start`` starts every EM iteration's E-step from the
+previous iteration's γ. The final E-step (θ's) always starts cold, so scoring the training day with
+``tol=var_tol`` still reproduces θ.
+
+Not done here: vector α.
 """
 from __future__ import annotations
 
@@ -63,9 +69,19 @@ class VarLDA:
         self.likelihoods: list = []
         self.bounds: list = []  # (iteration, bound, conv, α the E-step ran with), one per tracked iteration
         self.em_tol, self.estimate_alpha, self.converged = 0.0, False, False
+        self.var_tol, self.warm_start = 0.0, False
+        self.var_iters_trace: list = []  # mean E-step updates per document, one per EM iteration of the exit path
+        self._nit_sums: list = []        # the same as device scalars (Σ n_it), read back once per run
 
-    def _estep(self, want_gamma: bool):
-        return ops.vfold(*self._pairs, self.table, self.K, self.alpha, None, self.var_iters, want_gamma=want_gamma)
+    def _estep(self, want_gamma: bool, gamma0=None):
+        """(θ, γ) with ``want_gamma`` else θ. With ``var_tol`` and ``warm_start`` off this is ops.vfold,
+        as it always was; otherwise ops.vfold_exit from ``gamma0`` (None: the cold start)."""
+        if not (self.var_tol > 0 or self.warm_start):
+            return ops.vfold(*self._pairs, self.table, self.K, self.alpha, None, self.var_iters, want_gamma=want_gamma)
+        theta, gamma, n_it = ops.vfold_exit(*self._pairs, self.table, self.K, self.alpha, None, self.var_iters,
+                                            self.var_tol, gamma0)
+        self._nit_sums.append(n_it.sum())
+        return (theta, gamma) if want_gamma else theta
 
     def _bound(self, gamma: torch.Tensor) -> tuple[float, float]:
         """(bound, α statistic) of an E-step's γ against the table and α it ran with: one launch
@@ -79,7 +95,8 @@ class VarLDA:
 
     @traced("oni:vem.run")
     def run(self, em_iters: int = EM_ITERS, var_iters: int = VAR_ITERS, eval_every: int = 0, log=None,
-            em_tol: float = 0.0, estimate_alpha: bool = False) -> "VarLDA":
+            em_tol: float = 0.0, estimate_alpha: bool = False, var_tol: float = 0.0,
+            warm_start: bool = False) -> "VarLDA":
         """``em_iters`` rounds of E-step, responsibilities, statistics, table, then one final E-step
         against the final table. ``eval_every`` > 0 records the plug-in likelihood of every
         ``eval_every``-th iteration's E-step (θ and the table it ran against).
@@ -90,18 +107,29 @@ class VarLDA:
         to float32 (what the E-step kernel and a saved model carry). ``em_tol`` > 0: ``em_iters``
         is the maximum; EM stops after the M-step of an iteration that is at least the third of
         this call and has 0 ≤ conv ≤ em_tol (lda-c's loop, without its doubling of the E-step
-        iterations on a negative conv). With both off nothing of this runs."""
+        iterations on a negative conv). With both off nothing of this runs.
+
+        ``var_tol`` > 0 or ``warm_start``: the E-steps run ``ops.vfold_exit(max_iters=var_iters,
+        tol=var_tol)``, inside the EM loop from the previous iteration's γ when ``warm_start`` (the
+        first from the cold start); the final E-step always starts cold. ``var_iters_trace`` gets the
+        mean number of updates per document of every EM iteration's E-step, read back once at the end."""
         if em_iters < 0 or var_iters < 0:
             raise ValueError("em_iters and var_iters must be ≥ 0")
         if not em_tol >= 0:
             raise ValueError("em_tol must be ≥ 0")
+        if not (var_tol >= 0 and math.isfinite(var_tol)):
+            raise ValueError("var_tol must be finite and ≥ 0")
+        self.var_tol, self.warm_start = float(var_tol), bool(warm_start)
+        self._nit_sums, prev = [], None
         self.var_iters = int(var_iters)
         self.em_tol, self.estimate_alpha, self.converged = float(em_tol), bool(estimate_alpha), False
         track = self.em_tol > 0 or self.estimate_alpha
         ptr, wm_doc, wm_word, wm_pos = self._wm
         L_old = 0.0
         for it in range(int(em_iters)):
-            theta, gamma = self._estep(True)
+            theta, gamma = self._estep(True, prev)
+            if self.warm_start:
+                prev = gamma
             if eval_every > 0 and self.sweeps_done % eval_every == 0:
                 self._theta = theta
                 ll = self.record_likelihood()
@@ -128,6 +156,10 @@ class VarLDA:
             self._theta, self._gamma = self._estep(True)
         else:
             self._theta, self._gamma = self._estep(False), None
+        if self._nit_sums:  # the EM loop's E-steps, not the final one: one read for all of them
+            sums = torch.stack(self._nit_sums[:-1]).tolist() if len(self._nit_sums) > 1 else []
+            self.var_iters_trace += [s / max(1, int(self.c.D)) for s in sums]
+            self._nit_sums = []
         return self
 
     def theta(self) -> torch.Tensor:

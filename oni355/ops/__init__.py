@@ -1282,6 +1282,57 @@ def vfold(pair_word: torch.Tensor, pair_cnt: torch.Tensor, doc_pair_ptr: torch.T
     return (theta, gamma) if want_gamma else theta
 
 
+def vfold_exit(pair_word: torch.Tensor, pair_cnt: torch.Tensor, doc_pair_ptr: torch.Tensor, table: torch.Tensor,
+               K: int, alpha: float, prior: torch.Tensor | None = None, max_iters: int = 20, tol: float = 0.0,
+               gamma0: torch.Tensor | None = None):
+    """:func:`vfold` with a warm start and a per-document exit (k_vfold_exit;
+    :func:`oni355.ref.vfold_exit_spec.vfold_exit` is the specification). A document starts at its
+    ``gamma0`` row (f32 [D, KS]; None: the cold start a + N/K) and stops being updated once
+    Σ|γ_new − γ_old| ≤ ``tol`` · Σγ_new, or after ``max_iters`` updates. With ``tol`` = 0 and no
+    ``gamma0`` θ and γ are bit for bit :func:`vfold`'s with ``iters=max_iters``. Returns
+    (θ f32 [D, KS], γ f32 [D, KS], n_it int32 [D]: the updates each document received). CPU tensors
+    run the specification in float64, rounded to f32."""
+    from ..ref import vfold_exit_spec
+    P, D, K, max_iters = int(pair_word.numel()), int(doc_pair_ptr.numel()) - 1, int(K), int(max_iters)
+    _need(pair_word, torch.int32, "pair_word")
+    _need(pair_cnt, torch.int32, "pair_cnt", P)
+    _need(doc_pair_ptr, torch.int64, "doc_pair_ptr")
+    _need(table, torch.float32, "table")
+    if D < 0 or table.dim() != 2 or table.shape[1] % 4 or table.shape[1] > 256:
+        raise ValueError("vfold_exit: doc_pair_ptr int64 [D + 1] and table f32 [rows, KS], KS a multiple of 4 up to 256")
+    KS = int(table.shape[1])
+    if not 1 <= K <= KS or max_iters < 0:
+        raise ValueError("vfold_exit: 1 ≤ K ≤ KS and max_iters ≥ 0")
+    if prior is None and not alpha > 0:
+        raise ValueError("vfold_exit: alpha must be > 0")
+    tol = float(tol)
+    if not (tol >= 0 and tol <= float(np.finfo(np.float32).max)):
+        raise ValueError("vfold_exit: tol must be finite and ≥ 0")
+    dev = table.device
+    given = tuple(t for t in (prior, gamma0) if t is not None)
+    if prior is not None:
+        _need(prior, torch.float32, "prior", D * KS)
+    if gamma0 is not None:
+        _need(gamma0, torch.float32, "gamma0", D * KS)
+    if any(t.device != dev for t in (pair_word, pair_cnt, doc_pair_ptr) + given):
+        raise ValueError("vfold_exit: every tensor must be on the table's device")
+    if not _is_dev(table):
+        th, g, n_it, _ = vfold_exit_spec.vfold_exit(
+            pair_word.numpy(), pair_cnt.numpy(), doc_pair_ptr.numpy(), table.numpy(), K, float(alpha),
+            None if prior is None else prior.numpy().reshape(D, KS), max_iters, tol,
+            None if gamma0 is None else gamma0.numpy().reshape(D, KS))
+        return torch.from_numpy(th.astype(np.float32)), torch.from_numpy(g.astype(np.float32)), torch.from_numpy(n_it)
+    theta = torch.empty(D, KS, dtype=torch.float32, device=dev)
+    gamma = torch.empty(D, KS, dtype=torch.float32, device=dev)
+    n_it = torch.empty(D, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().oni_vfold_exit(_lib.ptr(pair_word) if P else None, _lib.ptr(pair_cnt) if P else None,
+                                         _lib.ptr(doc_pair_ptr), D, _lib.ptr(table), KS, K, float(np.float32(alpha)),
+                                         _lib.ptr(prior), max_iters, float(np.float32(tol)), _lib.ptr(gamma0),
+                                         _lib.ptr(theta) if D else None, _lib.ptr(gamma) if D else None,
+                                         _lib.ptr(n_it) if D else None, _lib.stream()), "oni_vfold_exit")
+    return theta, gamma, n_it
+
+
 # ------------------------------------------------------------------------------------------------
 # variational EM (csrc/kernels/vem.hip): the M-step around vfold's E-step
 # ------------------------------------------------------------------------------------------------

@@ -107,6 +107,7 @@ _REGISTRY: dict[str, list] = {
     "oni_table_lookup": [vp, vp, i64, vp, i64, vp, vp, vp],
     "oni_doc_fit": [vp, vp, C.c_int, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, C.c_int, vp],
     "oni_vfold": [vp, vp, vp, i64, vp, C.c_int, C.c_int, f32, vp, C.c_int, vp, vp, vp],
+    "oni_vfold_exit": [vp, vp, vp, i64, vp, C.c_int, C.c_int, f32, vp, C.c_int, f32, vp, vp, vp, vp, vp],
     "oni_vem_resp": [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp, i64, i64, vp, vp, vp],
     "oni_vem_wsum": [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, vp, C.c_int, vp],
     "oni_vem_table": [vp, i64, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int, vp],

@@ -547,14 +547,17 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                     train: bool = True, timer: StageTimer | None = None, ldac_dir: str | None = None,
                     ldac_lag: int = 0, word_ids: torch.Tensor | None = None, n_event0: int = 0,
                     on_train=None, method: str = "gibbs", em_iters: int = 30, var_iters: int = 20,
-                    em_tol: float = 0.0, estimate_alpha: bool = False) -> LdaRun:
+                    em_tol: float = 0.0, estimate_alpha: bool = False, var_tol: float = 0.0,
+                    warm_start: bool = False) -> LdaRun:
     """Token keys → owner routing → local corpus → Gibbs LDA trained for ``sweeps`` sweeps.
 
     ``method`` ``"vem"`` trains the model by variational EM instead (models.vem_gpu.VarLDA:
     ``em_iters`` EM iterations of ``var_iters`` E-step iterations each, single GPU, no seed):
     ``sweeps``, ``seed``, ``burnin``, ONI_CHAINS, checkpoints, LAG snapshots and the MH burn-in
     do not apply. ``em_tol`` > 0 makes ``em_iters`` a maximum (EM stops on the variational bound's
-    relative change), ``estimate_alpha`` re-estimates α every EM iteration (``VarLDA.run``).
+    relative change), ``estimate_alpha`` re-estimates α every EM iteration, ``var_tol`` > 0 stops a
+    document's E-step on its relative γ change and ``warm_start`` starts each E-step from the
+    previous iteration's γ (``VarLDA.run``).
 
     ``word_ids`` (int32, from :func:`encode_words`) skips the vocabulary lookup of ``word_keys64``.
     Where :func:`fused_corpus` holds, ``doc_keys64`` may also be int32 u32 bits or the two int32
@@ -636,7 +639,7 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
         dcorpus = corpus_for(Gd) if Gd != G else None
     if method == "vem":
         return _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every,
-                          train, timer, log, on_train, em_tol, estimate_alpha)
+                          train, timer, log, on_train, em_tol, estimate_alpha, var_tol, warm_start)
     # ONI_CHAINS = C > 1: C independent chains of sweeps // C sweeps each (same total sweep count),
     # scored by the average of their pair scores (LdaRun.pair_scores): the top-N then depends less
     # on any one chain's seed. Dense samplers only, no checkpointing.
@@ -724,17 +727,22 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
 
 
 def check_train_method(method: str, em_iters: int, var_iters: int, comm=None, ckpt=None, ldac_dir=None,
-                       em_tol: float = 0.0, estimate_alpha: bool = False) -> None:
+                       em_tol: float = 0.0, estimate_alpha: bool = False, var_tol: float = 0.0,
+                       warm_start: bool = False) -> None:
     """``method`` of run_* : ``"gibbs"`` or ``"vem"``; what vem training does not combine with."""
     if method not in ("gibbs", "vem"):
         raise ValueError(f"method must be 'gibbs' or 'vem', not {method!r}")
     if method != "vem" and (em_tol or estimate_alpha):
         raise ValueError("em_tol and estimate_alpha belong to method='vem'")
+    if method != "vem" and (var_tol or warm_start):
+        raise ValueError("var_tol and warm_start belong to method='vem'")
     if method == "vem":
         if int(em_iters) < 0 or int(var_iters) < 0:
             raise ValueError("em_iters and var_iters must be ≥ 0")
         if not float(em_tol) >= 0:
             raise ValueError("em_tol must be ≥ 0")
+        if not 0 <= float(var_tol) < float("inf"):
+            raise ValueError("var_tol must be finite and ≥ 0")
         if comm is not None and comm.dist:
             raise NotImplementedError("vem training is single-GPU")
         if ckpt is not None or ldac_dir:
@@ -742,10 +750,12 @@ def check_train_method(method: str, em_iters: int, var_iters: int, comm=None, ck
 
 
 def vem_stats(method: str, em_iters: int, var_iters: int, em_tol: float = 0.0, estimate_alpha: bool = False,
-              run=None) -> dict:
+              run=None, var_tol: float = 0.0, warm_start: bool = False) -> dict:
     """What ``stats`` gains in vem mode (nothing with the Gibbs sampler). With ``em_tol`` > 0 or
     ``estimate_alpha`` also what the trained ``run`` (LdaRun) ended with: the variational bound of
-    its final E-step, the final α, the EM iterations run and whether the exit was the tolerance."""
+    its final E-step, the final α, the EM iterations run and whether the exit was the tolerance.
+    With ``var_tol`` > 0 or ``warm_start``: both, and the mean E-step updates per document of the
+    first and the last EM iteration."""
     if method != "vem":
         return {}
     out = {"train_method": "vem", "em_iters": int(em_iters), "var_iters": int(var_iters)}
@@ -753,11 +763,15 @@ def vem_stats(method: str, em_iters: int, var_iters: int, em_tol: float = 0.0, e
         m, elbo = run.model, run.model.bound()
         out.update(elbo=elbo, elbo_per_token=elbo / max(int(run.corpus.T), 1), alpha_final=float(m.alpha),
                    em_iters_done=int(m.sweeps_done), em_converged=bool(m.converged))
+    if var_tol > 0 or warm_start:
+        tr = run.model.var_iters_trace if run is not None else []
+        out.update(var_tol=float(var_tol), warm_start=bool(warm_start),
+                   var_iters_mean_first=tr[0] if tr else None, var_iters_mean_last=tr[-1] if tr else None)
     return out
 
 
 def _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every, train,
-               timer, log, on_train, em_tol=0.0, estimate_alpha=False) -> LdaRun:
+               timer, log, on_train, em_tol=0.0, estimate_alpha=False, var_tol=0.0, warm_start=False) -> LdaRun:
     """The ``init`` / ``train`` stages of :func:`build_and_train` with ``method="vem"``."""
     from ..models.vem_gpu import VarLDA
     with timer.stage("init"):
@@ -768,7 +782,8 @@ def _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters
     with timer.stage("train"):
         if on_train is not None:
             on_train()
-        model.run(em_iters, var_iters, eval_every=eval_every, log=log, em_tol=em_tol, estimate_alpha=estimate_alpha)
+        model.run(em_iters, var_iters, eval_every=eval_every, log=log, em_tol=em_tol, estimate_alpha=estimate_alpha,
+                  var_tol=var_tol, warm_start=warm_start)
     model.close()
     if not model.likelihoods or model.likelihoods[-1][0] != model.sweeps_done:
         model.record_likelihood()
@@ -1112,9 +1127,10 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
                           feedback=None, row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None,
                           timer: StageTimer | None = None, ldac_dir: str | None = None,
                           ldac_lag: int = 0, key_bits: int = 64, method: str = "gibbs", em_iters: int = 30,
-                          var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False) -> SingleResult:
+                          var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False,
+                          var_tol: float = 0.0, warm_start: bool = False) -> SingleResult:
     """Shared DNS/proxy path: one (doc, word) token per event; score = θ_doc·φ_word (C24)."""
-    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha)
+    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha, var_tol, warm_start)
     dev = doc_keys64.device
     timer = timer or StageTimer(dev)
     with timer.stage("vocab"):
@@ -1131,7 +1147,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     run = build_and_train(dk, None, wts, vocab, K, alpha, beta, seed, sweeps, chunk_len, comm, eval_every=eval_every, burnin=burnin,
                           ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag, word_ids=wids,
                           n_event0=n, method=method, em_iters=em_iters, var_iters=var_iters, em_tol=em_tol,
-                          estimate_alpha=estimate_alpha)
+                          estimate_alpha=estimate_alpha, var_tol=var_tol, warm_start=warm_start)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     if run.route is not None:
         with timer.stage("score_prep"):
@@ -1158,7 +1174,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     stats = run.corpus.stats()
     stats.update({"events": int(doc_keys64.numel()),
                   "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
-    stats.update(vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run))
+    stats.update(vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run, var_tol, warm_start))
     return SingleResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(),
                         words=words.cpu().numpy().view(np.uint64), timings=t, stats=stats, lda=run)
 
@@ -1199,30 +1215,45 @@ def top_list_mismatch(model, top_domains, user_domain: str | None, log=None) -> 
     return bool(bad)
 
 
-def check_infer_method(method: str, iters: int) -> None:
-    """The ``method`` / ``iters`` arguments of the score_* functions."""
+def check_infer_method(method: str, iters: int, infer_tol: float = 0.0) -> None:
+    """The ``method`` / ``iters`` / ``infer_tol`` arguments of the score_* functions."""
     if method not in ("gibbs", "vb"):
         raise ValueError('method must be "gibbs" or "vb"')
     if method == "vb" and int(iters) < 0:
         raise ValueError("iters must be ≥ 0")
+    if not 0 <= float(infer_tol) < float("inf"):
+        raise ValueError("infer_tol must be finite and ≥ 0")
+    if method != "vb" and infer_tol:
+        raise ValueError('infer_tol belongs to method="vb"')
+
+
+def vb_stats(fold, iters: int, infer_tol: float) -> dict:
+    """What ``stats`` gains with ``method="vb"``; with ``infer_tol`` > 0 also the tolerance and the
+    mean number of updates a document received."""
+    out = {"infer_method": "vb", "infer_iters": int(iters)}
+    if infer_tol > 0:
+        out.update(infer_tol=float(infer_tol), infer_iters_mean=fold.iters_mean())
+    return out
 
 
 @traced("oni:score_single_doc_events")
 def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, model, tol: float, maxresults: int,
                             sweeps: int, avg_last: int, seed: int, chunk_len: int, row_offset: int,
                             timer: StageTimer, fuse: bool = True, prior_mass: float = 0.0,
-                            fit: bool = False, method: str = "gibbs", iters: int = 20) -> SingleResult:
+                            fit: bool = False, method: str = "gibbs", iters: int = 20,
+                            infer_tol: float = 0.0) -> SingleResult:
     """The DNS / proxy half of scoring against a saved model, after wordification: one (doc, word)
     token per event. Word ids through the model's vocabulary (an unseen word → id V, the
     out-of-vocabulary row), the batch's own documents folded in against the frozen table
     (models.foldin.FoldIn, optionally under per-IP priors), θ, then the one-sided score plan and
     top-N against the model's table -- :func:`oni355.pipeline.flow.score_flow` for one endpoint.
     ``fit``: also the batch's likelihood under the model (:func:`batch_fit`), in a ``fit`` stage.
-    ``method`` / ``iters``: ``"vb"`` takes θ from the variational fold-in (models.foldin.VarFoldIn)."""
+    ``method`` / ``iters`` / ``infer_tol``: ``"vb"`` takes θ from the variational fold-in
+    (models.foldin.VarFoldIn), with ``infer_tol`` > 0 under its per-document exit."""
     from ..models.foldin import FoldIn, VarFoldIn
     from ..models.gibbs import tiling_for
     from ..ref.foldin_spec import V6_KEY_BASE
-    check_infer_method(method, iters)
+    check_infer_method(method, iters, infer_tol)
     dev = doc_keys64.device
     n = int(doc_keys64.numel())
     with timer.stage("vocab"):
@@ -1253,7 +1284,7 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
                 n_prior = int(((mkeys[pos] == udoc) & (udoc < V6_KEY_BASE)).sum())
     with timer.stage("foldin"):
         if method == "vb":
-            fold = VarFoldIn(corpus, table, K, model.alpha, prior=prior).run(iters)
+            fold = VarFoldIn(corpus, table, K, model.alpha, prior=prior).run(iters, infer_tol)
         else:
             fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
             fold.run(sweeps, avg_last)
@@ -1286,7 +1317,7 @@ def score_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor,
     stats.update({"events": n, "loglik": None, "mode": "infer", "n_oov_tokens": int(oov.item()),
                   "foldin_launches": sum(fold.launches.values())})
     if method == "vb":
-        stats.update({"infer_method": "vb", "infer_iters": int(iters)})
+        stats.update(vb_stats(fold, iters, infer_tol))
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
     if bfit is not None:

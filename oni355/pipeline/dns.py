@@ -122,10 +122,11 @@ def run_dns(cols: dict, K: int = 50, sweeps: int = 200, tol: float = 1.0, maxres
             feedback: dict | None = None, dupfactor: int = 1000, row_offset: int = 0, eval_every: int = 0, burnin: int = 0,
             ckpt=None, log=None, ldac_dir: str | None = None, ldac_lag: int = 0,
             device_cols: dict | None = None, method: str = "gibbs", em_iters: int = 30,
-            var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False) -> common.SingleResult:
+            var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False,
+            var_tol: float = 0.0, warm_start: bool = False) -> common.SingleResult:
     """``device_cols``: :func:`host_arrays` already on the device (e.g. prefetched by
     io.staging.Prefetcher while the previous day computed). ``method`` / ``em_iters`` /
-    ``var_iters`` / ``em_tol`` / ``estimate_alpha``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
+    ``var_iters`` / ``em_tol`` / ``estimate_alpha`` / ``var_tol`` / ``warm_start``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
     timer = StageTimer(device)
     with timer.stage("h2d"):
         d = dict(device_cols) if device_cols is not None else to_device(cols, device)
@@ -149,7 +150,8 @@ def run_dns(cols: dict, K: int = 50, sweeps: int = 200, tol: float = 1.0, maxres
                                        feedback=fb, row_offset=row_offset, eval_every=eval_every, burnin=burnin, ckpt=ckpt, log=log,
                                        timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag,
                                        key_bits=40, method=method, em_iters=em_iters, var_iters=var_iters,
-                                       em_tol=em_tol, estimate_alpha=estimate_alpha)
+                                       em_tol=em_tol, estimate_alpha=estimate_alpha, var_tol=var_tol,
+                                       warm_start=warm_start)
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in cuts.items()}
     res.stats["features"] = feats
     return res
@@ -172,7 +174,8 @@ def score_dns(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweep
               seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
               top_domains=None, user_domain: str | None = None, feedback: dict | None = None, chunk_len: int = 0,
               row_offset: int = 0, log=None, fuse: bool = True, prior_mass: float = 0.0,
-              fit: bool = False, method: str = "gibbs", iters: int = 20) -> common.SingleResult:
+              fit: bool = False, method: str = "gibbs", iters: int = 20,
+              infer_tol: float = 0.0) -> common.SingleResult:
     """Score a batch of DNS responses against a saved model (``model``: models.saved.SavedModel of
     source ``dns``) instead of training on it: words from the model's cuts, the given top-domain
     list and the model's user domain (``user_domain`` None; another list or domain is allowed and
@@ -196,7 +199,8 @@ def score_dns(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, sweep
         words, _, feats = featurize(d, None, top_set(top_domains), user_domain, cuts=model.cuts)
     res = common.score_single_doc_events(common.u32_to_i64(d["ip_dst"]), words, model, tol, maxresults, sweeps,
                                          avg_last, seed, chunk_len, row_offset, timer, fuse=fuse,
-                                         prior_mass=prior_mass, fit=fit, method=method, iters=iters)
+                                         prior_mass=prior_mass, fit=fit, method=method, iters=iters,
+                                         infer_tol=infer_tol)
     res.stats["model_top_mismatch"] = mismatch
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in model.cuts.items()}
     res.stats["features"] = feats

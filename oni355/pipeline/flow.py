@@ -227,7 +227,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
              row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None, ldac_dir: str | None = None,
              ldac_lag: int = 0, device_cols: dict | None = None, on_train=None, method: str = "gibbs",
              em_iters: int = 30, var_iters: int = 20, em_tol: float = 0.0,
-             estimate_alpha: bool = False) -> FlowResult:
+             estimate_alpha: bool = False, var_tol: float = 0.0, warm_start: bool = False) -> FlowResult:
     """Full suspicious-connects for one (rank-local shard of a) day of flows. ``device_cols``:
     the day's :data:`DEVICE_COLS` already on the device (e.g. from io.staging.Prefetcher, which
     uploaded them while the previous day computed); ``cols`` still supplies the host rows.
@@ -237,8 +237,12 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
     ``train_method``, ``em_iters`` and ``var_iters``. ``em_tol`` > 0 stops EM once the variational
     bound's relative change is in [0, em_tol] (``em_iters`` is then the maximum); ``estimate_alpha``
     re-estimates α every EM iteration. With either, ``stats`` also carries ``elbo``,
-    ``elbo_per_token``, ``alpha_final``, ``em_iters_done`` and ``em_converged``."""
-    common.check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha)
+    ``elbo_per_token``, ``alpha_final``, ``em_iters_done`` and ``em_converged``. ``var_tol`` > 0
+    stops a document's E-step once its relative γ change is ≤ var_tol (``var_iters`` is then the
+    maximum), ``warm_start`` starts every EM iteration's E-step from the previous one's γ; with either,
+    ``stats`` carries both and ``var_iters_mean_first`` / ``var_iters_mean_last``."""
+    common.check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha, var_tol,
+                              warm_start)
     timer = StageTimer(device)
     if device_cols is None:
         cols, feedback = with_ipv6_keys(cols, comm, (feedback,)) if feedback else (with_ipv6_keys(cols, comm), None)
@@ -275,7 +279,8 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
     run = common.build_and_train(doc_keys, None, weights, vocab, K, alpha, beta, seed, sweeps, chunk_len, comm,
                                  eval_every=eval_every, burnin=burnin, ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir,
                                  ldac_lag=ldac_lag, word_ids=wids, n_event0=n, on_train=on_train, method=method,
-                                 em_iters=em_iters, var_iters=var_iters, em_tol=em_tol, estimate_alpha=estimate_alpha)
+                                 em_iters=em_iters, var_iters=var_iters, em_tol=em_tol, estimate_alpha=estimate_alpha,
+                                 var_tol=var_tol, warm_start=warm_start)
 
     # ---- scoring --------------------------------------------------------------------------------
     hist = torch.zeros(2048, dtype=torch.int32, device=d["sip"].device)
@@ -331,7 +336,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
         wparts = allp[:, 3:5].to(torch.int32)
     stats = run.corpus.stats()
     stats.update({"n_flows": n, "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
-    stats.update(common.vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run))
+    stats.update(common.vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run, var_tol, warm_start))
     return FlowResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), src_scores=parts[:, 0].cpu().numpy(),
                       dst_scores=parts[:, 1].cpu().numpy(), src_words=wparts[:, 0].cpu().numpy().view(np.uint32),
                       dst_words=wparts[:, 1].cpu().numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats,
@@ -346,7 +351,7 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
                seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
                feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
                fuse: bool = True, prior_mass: float = 0.0, fit: bool = False, method: str = "gibbs",
-               iters: int = 20) -> FlowResult:
+               iters: int = 20, infer_tol: float = 0.0) -> FlowResult:
     """Score a batch of flows against a saved model (``model``: models.saved.SavedModel) instead of
     training on it: words from the model's cuts, ids through its vocabulary (unseen words → the
     out-of-vocabulary row), the batch's own IP documents folded in against the frozen φ
@@ -363,7 +368,9 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
     ``method``: ``"gibbs"`` (the default) samples θ with the fold-in chain; ``"vb"`` computes it with
     ``iters`` iterations of the deterministic variational fold-in (models.foldin.VarFoldIn):
     ``sweeps``, ``avg_last`` and ``seed`` are then ignored and ``stats`` carries ``infer_method`` and
-    ``infer_iters``."""
+    ``infer_iters``. ``infer_tol`` > 0 (``"vb"`` only): a document stops being updated once its
+    relative γ change is ≤ infer_tol (ops.vfold_exit; ``iters`` is then the maximum) and ``stats``
+    also carries ``infer_tol`` and ``infer_iters_mean``."""
     from ..models.corpus import auto_chunk_len, build_corpus
     from ..models.foldin import FoldIn, VarFoldIn
     from ..models.gibbs import tiling_for
@@ -371,7 +378,7 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
         raise NotImplementedError("fold-in scoring is single-GPU")
     if model.source != "flow":
         raise ValueError(f"a {model.source} model cannot score flows")
-    common.check_infer_method(method, iters)
+    common.check_infer_method(method, iters, infer_tol)
     if feedback and log:
         log("analyst feedback is ignored when scoring against a saved model")
     prior_mass = float(prior_mass)
@@ -422,7 +429,7 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
                 n_prior = int(((mkeys[pos] == udoc) & (udoc < V6_KEY_BASE)).sum())
     with timer.stage("foldin"):
         if method == "vb":
-            fold = VarFoldIn(corpus, table, K, model.alpha, prior=prior).run(iters)
+            fold = VarFoldIn(corpus, table, K, model.alpha, prior=prior).run(iters, infer_tol)
         else:
             fold = FoldIn(corpus, table, K, model.alpha, seed, fuse=fuse, prior=prior)
             fold.run(sweeps, avg_last)
@@ -460,7 +467,7 @@ def score_flow(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swee
     stats.update({"n_flows": n, "loglik": None, "mode": "infer", "n_oov_tokens": int(oov.item()),
                   "foldin_launches": sum(fold.launches.values())})
     if method == "vb":
-        stats.update({"infer_method": "vb", "infer_iters": int(iters)})
+        stats.update(common.vb_stats(fold, iters, infer_tol))
     if prior is not None:
         stats.update({"n_prior_docs": n_prior, "prior_mass": prior_mass})
     if bfit is not None:

@@ -228,10 +228,11 @@ def run_proxy(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxr
               dupfactor: int = 1000, row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None,
               log=None, ldac_dir: str | None = None, ldac_lag: int = 0,
               device_cols: dict | None = None, method: str = "gibbs", em_iters: int = 30,
-            var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False) -> common.SingleResult:
+            var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False,
+            var_tol: float = 0.0, warm_start: bool = False) -> common.SingleResult:
     """``device_cols``: :func:`host_arrays` already on the device (e.g. prefetched by
     io.staging.Prefetcher while the previous day computed). ``method`` / ``em_iters`` /
-    ``var_iters`` / ``em_tol`` / ``estimate_alpha``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
+    ``var_iters`` / ``em_tol`` / ``estimate_alpha`` / ``var_tol`` / ``warm_start``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
     timer = StageTimer(device)
     with timer.stage("h2d"):
         d = dict(device_cols) if device_cols is not None else \
@@ -249,7 +250,8 @@ def run_proxy(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxr
                                        feedback=fb, row_offset=row_offset, eval_every=eval_every, burnin=burnin, ckpt=ckpt, log=log,
                                        timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag,
                                        key_bits=34, method=method, em_iters=em_iters, var_iters=var_iters,
-                                       em_tol=em_tol, estimate_alpha=estimate_alpha)
+                                       em_tol=em_tol, estimate_alpha=estimate_alpha, var_tol=var_tol,
+                                       warm_start=warm_start)
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in cuts.items()}
     res.stats["ua_table"] = ua_table
     return res
@@ -270,7 +272,7 @@ def score_proxy(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swe
                 seed: int = 0x0D15EA5E, device="cpu", device_cols: dict | None = None, comm: Comm | None = None,
                 top_domains=None, feedback: dict | None = None, chunk_len: int = 0, row_offset: int = 0, log=None,
                 fuse: bool = True, prior_mass: float = 0.0, fit: bool = False, method: str = "gibbs",
-                iters: int = 20) -> common.SingleResult:
+                iters: int = 20, infer_tol: float = 0.0) -> common.SingleResult:
     """Score a batch of proxy requests against a saved model (``model``: models.saved.SavedModel of
     source ``proxy``) instead of training on it: words from the model's cuts and its user-agent
     frequency table (a user agent the training day never saw counts 0) and the given top-domain
@@ -295,7 +297,8 @@ def score_proxy(cols: dict, model, tol: float = 1.0, maxresults: int = 3000, swe
         words, _, _ = featurize(cols, device, None, top_set(top_domains), d=d, day=(model.cuts, ua))
     res = common.score_single_doc_events(common.u32_to_i64(d["clientip"]), words, model, tol, maxresults, sweeps,
                                          avg_last, seed, chunk_len, row_offset, timer, fuse=fuse,
-                                         prior_mass=prior_mass, fit=fit, method=method, iters=iters)
+                                         prior_mass=prior_mass, fit=fit, method=method, iters=iters,
+                                         infer_tol=infer_tol)
     res.stats["model_top_mismatch"] = mismatch
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in model.cuts.items()}
     return res

@@ -50,9 +50,11 @@ HIP_FLAGS = [
 ]
 # per-file additions: fit.hip adds f32 pairs lane-wise all over (the scan, the butterflies); it and
 # vfold.hip (fixed-order f32 sums) are built without the packed-f32 VALU forms so that every such
-# add is the plain scalar instruction; vem.hip (the f32 dot of its pair pass) likewise
+# add is the plain scalar instruction; vem.hip (the f32 dot of its pair pass) and vfold_exit.hip
+# (k_vfold's arithmetic, bit for bit) likewise
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_FILE_FLAGS = {"fit.hip": _NO_PK_F32, "vfold.hip": _NO_PK_F32, "vem.hip": _NO_PK_F32}
+HIP_FILE_FLAGS = {"fit.hip": _NO_PK_F32, "vfold.hip": _NO_PK_F32, "vem.hip": _NO_PK_F32,
+                  "vfold_exit.hip": _NO_PK_F32}
 CXX_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-fopenmp", "-Wall", "-Wno-unused-function",
              "-I", os.path.join(CSRC, "native")]
 
