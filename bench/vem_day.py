@@ -33,6 +33,14 @@ tolerance from the cold start and from the previous γ, and what the lockstep of
 (Σ n_it against Σ over rounds of documents × the round's largest n_it).
 
   python bench/vem_day.py --var-tol 1e-3,1e-5 --out profiles/vem/exit_flow_12.5M_k20.json
+
+``--cvb-iters N`` runs a fourth comparison: Gibbs, vem (fixed ``--em-iters`` × ``--var-iters``) and batch
+CVB0 (method="cvb0", N iterations) days alternating in one process; per variant ms per day and of the
+train stage and the planted recall; the overlap of the cvb0 top-N with every Gibbs seed's and vem's next
+to the Gibbs seed-to-seed overlap; the cvb0 likelihood trace per iteration; and, with device events,
+ops.cvb0_update and the word sum each alone next to a device copy of the bytes an iteration must move.
+
+  python bench/vem_day.py --cvb-iters 100 --out profiles/cvb0/flow_12.5M_k20.json
 """
 from __future__ import annotations
 
@@ -239,8 +247,85 @@ def exit_ab(a, run, day, kw: dict, planted: set, dev) -> int:
     return 0
 
 
+def cvb_ab(a, run, day, kw: dict, planted: set, dev) -> int:
+    """The ``--cvb-iters`` comparison of the module text."""
+    import torch
+
+    from oni355 import ops
+    vkw = dict(method="vem", em_iters=a.em_iters, var_iters=a.var_iters)
+    ckw = dict(method="cvb0", cvb_iters=a.cvb_iters)
+    variants = {"gibbs": lambda r: run(day.cols, sweeps=a.sweeps, seed=101 + r, **kw),
+                "vem": lambda r: run(day.cols, **vkw, **kw), "cvb0": lambda r: run(day.cols, **ckw, **kw)}
+    iters = {"gibbs": a.sweeps, "vem": a.em_iters, "cvb0": a.cvb_iters}
+    for fn in variants.values():  # one untimed day each
+        fn(0)
+    days = {n: [] for n in variants}
+    tops = {n: [] for n in variants}
+    for r in range(a.rounds):
+        for name, fn in variants.items():
+            torch.cuda.synchronize(dev)
+            ts = time.perf_counter()
+            res = fn(r)
+            torch.cuda.synchronize(dev)
+            wall = time.perf_counter() - ts
+            t = res.timings
+            train_ms = t.get("train_dev_s", t.get("train_s", 0.0)) * 1e3
+            rows = set(res.rows.tolist())
+            line = {"variant": name, "round": r, "day_ms": round(wall * 1e3, 2), "train_ms": round(train_ms, 3),
+                    "init_ms": round(t.get("init_dev_s", t.get("init_s", 0.0)) * 1e3, 3),
+                    "ms_per_iter": round(train_ms / max(iters[name], 1), 4),
+                    "planted_recall_topN": round(len(rows & planted) / max(len(planted), 1), 4),
+                    "loglik": res.stats["loglik"]}
+            days[name].append(line)
+            tops[name].append(rows)
+            print(json.dumps(line), flush=True)
+            del res
+    summary = {n: {"day_ms_median": statistics.median(x["day_ms"] for x in v),
+                   "day_ms_spread": round(max(x["day_ms"] for x in v) - min(x["day_ms"] for x in v), 2),
+                   "train_ms_median": statistics.median(x["train_ms"] for x in v),
+                   "ms_per_iter_median": statistics.median(x["ms_per_iter"] for x in v),
+                   "planted_recall_topN": [x["planted_recall_topN"] for x in v]} for n, v in days.items()}
+    n_top, g, c = max(len(tops["cvb0"][0]), 1), tops["gibbs"], tops["cvb0"][0]
+    overlap = {"cvb0_vs_cvb0": [round(len(c & x) / n_top, 4) for x in tops["cvb0"][1:]],
+               "cvb0_vs_gibbs": [round(len(c & x) / n_top, 4) for x in g],
+               "cvb0_vs_vem": round(len(c & tops["vem"][0]) / n_top, 4),
+               "gibbs_vs_gibbs": [round(len(g[i] & g[j]) / n_top, 4) for i in range(len(g)) for j in range(i + 1, len(g))]}
+    # one iteration's two ops, each alone with device events, and a device copy of the bytes the
+    # iteration must move (r read and written by the update, read again by the word sum)
+    traced = run(day.cols, eval_every=1, **ckw, **kw)
+    m = traced.lda.model
+    from oni355.models.cvb0_gpu import CvbLDA
+    m = CvbLDA(m.c, m.K, m.alpha, m.beta).run(3)
+    ptr, wm_src, wm_word, wm_cnt = m._wm
+    P, KS = int(m._r.shape[0]), m.KS
+    src, dst = torch.empty(P * KS * 3 // 2, dtype=torch.float32, device=dev), torch.empty(P * KS * 3 // 2, dtype=torch.float32, device=dev)
+    ops_ms = {"cvb0_update": _timed(lambda: ops.cvb0_update(m._r, m.n_dk, m.n_wk, m.n_k, *m._pairs, m._ptr, m.K, m.alpha,
+                                                            m.beta, m.V), a.op_reps),
+              "word_sum": _timed(lambda: ops.vem_wsum(m._r, wm_cnt, m._ones, ptr, wm_src, wm_word, m.V, m.K), a.op_reps),
+              "table": _timed(lambda: ops.vem_table(m.n_wk, m.K, m.beta), a.op_reps),
+              "copy_same_bytes": _timed(lambda: dst.copy_(src), a.op_reps)}
+    moved = 3 * P * KS * 4
+    it_ms = ops_ms["cvb0_update"]["ms_median"] + ops_ms["word_sum"]["ms_median"]
+    bw = {"bytes_per_iteration": moved, "copy_GBps": round(moved / ops_ms["copy_same_bytes"]["ms_median"] / 1e6, 1),
+          "iteration_GBps": round(moved / it_ms / 1e6, 1),
+          "fraction_of_copy": round(ops_ms["copy_same_bytes"]["ms_median"] / it_ms, 4)}
+    trace = [[int(i), float(ll)] for i, ll in traced.lda.model.likelihoods]
+    out = {"source": a.source, "flows": a.flows, "topics": a.topics, "gibbs_sweeps": a.sweeps, "em_iters": a.em_iters,
+           "var_iters": a.var_iters, "cvb_iters": a.cvb_iters, "rounds": a.rounds, "pairs": P, "docs": int(m.c.D),
+           "V": m.V, "KS": KS, "summary": summary, "top_overlap": overlap, "ops_ms": ops_ms, "bandwidth": bw,
+           "loglik_trace": trace, "days": days}
+    print(json.dumps({"summary": summary, "top_overlap": overlap, "ops_ms": ops_ms, "bandwidth": bw}), flush=True)
+    print(json.dumps({"loglik_trace": trace}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cvb-iters", type=int, default=0, help="> 0: Gibbs, vem and cvb0 days alternating instead")
     ap.add_argument("--flows", type=int, default=12_500_000)
     ap.add_argument("--topics", type=int, default=20)
     ap.add_argument("--sweeps", type=int, default=200, help="Gibbs sweeps")
@@ -276,6 +361,8 @@ def main() -> int:
             return dns.run_dns(cols, user_domain="intel", **k)
     planted = set(np.asarray(day.anomaly_rows).tolist())
     print(f"generated {a.flows} {a.source} events in {time.perf_counter() - t0:.1f} s", flush=True)
+    if a.cvb_iters > 0:
+        return cvb_ab(a, run, day, kw, planted, dev)
     if a.em_tol > 0:
         return bound_ab(a, run, day, kw, planted, dev)
     if a.var_tol:

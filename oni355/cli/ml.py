@@ -74,9 +74,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--infer-prior-mass", type=float, default=0.0, metavar="M",
                     help="--model: fold an IP the model knows in under its training-day topic profile, weighted "
                          "by at most M pseudo-tokens (0: off, every IP starts from the flat prior)")
-    ap.add_argument("--train-method", choices=["gibbs", "vem"], default="gibbs",
-                    help="how the day's model is trained: gibbs (default, the collapsed-Gibbs sampler) or vem "
-                         "(variational EM, lda-c's estimator: deterministic, no seed, single GPU; --sweeps unused)")
+    ap.add_argument("--train-method", choices=["gibbs", "vem", "cvb0"], default="gibbs",
+                    help="how the day's model is trained: gibbs (default, the collapsed-Gibbs sampler), vem "
+                         "(variational EM, lda-c's estimator: deterministic, no seed, single GPU; --sweeps unused) "
+                         "or cvb0 (batch collapsed variational Bayes: deterministic, no seed, single GPU; --sweeps unused)")
+    ap.add_argument("--cvb-iters", type=int, default=None, metavar="N",
+                    help="--train-method cvb0: iterations (default 100)")
     ap.add_argument("--em-iters", type=int, default=None, metavar="N",
                     help="--train-method vem: EM iterations (default 30)")
     ap.add_argument("--var-iters", type=int, default=None, metavar="N",
@@ -289,15 +292,20 @@ def main(argv=None) -> int:
             raise SystemExit(f"oni-ml: {flag} belongs to variational EM; it needs --train-method vem")
         if val is not None and val < 0:
             raise SystemExit(f"oni-ml: {flag} must be ≥ 0")
-    if a.train_method == "vem":
+    if a.cvb_iters is not None and a.train_method != "cvb0":
+        raise SystemExit("oni-ml: --cvb-iters belongs to batch CVB0; it needs --train-method cvb0")
+    if a.cvb_iters is not None and a.cvb_iters < 0:
+        raise SystemExit("oni-ml: --cvb-iters must be ≥ 0")
+    if a.train_method in ("vem", "cvb0"):
+        tm = a.train_method
         if gpus_asked > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit("oni-ml: --train-method vem is single-GPU; drop --gpus")
+            raise SystemExit(f"oni-ml: --train-method {tm} is single-GPU; drop --gpus")
         for flag, val in (("--ckpt-dir", a.ckpt_dir), ("--ldac-out", a.ldac_out), ("--model", a.model)):
             if val:
-                raise SystemExit(f"oni-ml: --train-method vem does not combine with {flag} (no checkpoints, no lda-c "
+                raise SystemExit(f"oni-ml: --train-method {tm} does not combine with {flag} (no checkpoints, no lda-c "
                                  "files, and --model trains nothing)")
         if a.max_restarts > 0:
-            raise SystemExit("oni-ml: --train-method vem does not combine with --max-restarts (no checkpoints)")
+            raise SystemExit(f"oni-ml: --train-method {tm} does not combine with --max-restarts (no checkpoints)")
     if a.infer_fit and not a.model:
         raise SystemExit("oni-ml: --infer-fit reports the fit of a saved model; it needs --model FILE")
     for flag, val in (("--infer-method", a.infer_method), ("--infer-iters", a.infer_iters), ("--infer-tol", a.infer_tol)):
@@ -382,6 +390,8 @@ def main(argv=None) -> int:
         common_kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
                          var_iters=20 if a.var_iters is None else a.var_iters, em_tol=a.em_tol or 0.0,
                          estimate_alpha=a.estimate_alpha, var_tol=a.var_tol or 0.0, warm_start=a.warm_start)
+    if a.train_method == "cvb0":
+        common_kw.update(method="cvb0", cvb_iters=100 if a.cvb_iters is None else a.cvb_iters)
     if a.ldac_out and a.ldac_lag > 0:
         common_kw.update(ldac_dir=os.path.join(a.ldac_out, f"rank{rank}") if world > 1 else a.ldac_out,
                          ldac_lag=a.ldac_lag)
@@ -483,6 +493,8 @@ def _main_days(a, cfg, comm, device, dates: list[str], log) -> int:
         kw.update(method="vem", em_iters=30 if a.em_iters is None else a.em_iters,
                   var_iters=20 if a.var_iters is None else a.var_iters, em_tol=a.em_tol or 0.0,
                   estimate_alpha=a.estimate_alpha, var_tol=a.var_tol or 0.0, warm_start=a.warm_start)
+    if a.train_method == "cvb0":
+        kw.update(method="cvb0", cvb_iters=100 if a.cvb_iters is None else a.cvb_iters)
     if a.source == "dns":
         kw.update(top_domains=top, user_domain=cfg.USER_DOMAIN)
     elif a.source == "proxy":

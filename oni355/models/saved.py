@@ -161,7 +161,10 @@ class SavedModel:
         if run.route is not None or run.extra_models:
             raise NotImplementedError("models are saved from single-GPU, single-chain runs")
         K = m.K
-        if hasattr(m, "phi_oov"):  # variational EM (models.vem_gpu.VarLDA): no seed, its own unseen-word row
+        if getattr(m, "train_method", None) == "cvb0":  # batch CVB0 (models.cvb0_gpu.CvbLDA): no seed either
+            prv = {"train_method": "cvb0", "cvb_iters": int(m.sweeps_done), "tree_hash": prov.tree_hash("hip")}
+            phi_oov = m.phi_oov().cpu().numpy()
+        elif hasattr(m, "phi_oov"):  # variational EM (models.vem_gpu.VarLDA): no seed, its own unseen-word row
             prv = {"train_method": "vem", "em_iters": int(m.sweeps_done), "var_iters": int(m.var_iters),
                    "tree_hash": prov.tree_hash("hip"), "em_tol": float(m.em_tol),
                    "estimate_alpha": bool(m.estimate_alpha), "var_tol": float(m.var_tol),

@@ -1503,3 +1503,118 @@ def vem_bound(gamma: torch.Tensor, table: torch.Tensor, pair_doc: torch.Tensor, 
                                         alpha, _lib.ptr(doc) if D else None, _lib.ptr(tot), _lib.ptr(scratch),
                                         int(scratch.numel()), int(grid or 0), _lib.stream()), "oni_vem_bound")
     return VemBound(doc, tot)
+
+
+# ------------------------------------------------------------------------------------------------
+# batch CVB0 (csrc/kernels/cvb0.hip): responsibilities per distinct pair, expected counts
+# ------------------------------------------------------------------------------------------------
+def _cvb_ks(K: int, KS: int, what: str) -> tuple[int, int]:
+    K, KS = int(K), int(KS)
+    if KS % 4 or KS > 256 or not 1 <= K <= KS:
+        raise ValueError(f"{what}: KS a multiple of 4 up to 256, 1 ≤ K ≤ KS")
+    return K, KS
+
+
+def cvb0_init(pair_word: torch.Tensor, V: int, K: int, KS: int) -> torch.Tensor:
+    """The responsibility rows r f32 [P, KS] CVB0 starts from (k_cvb_init): the hash init of vem,
+    t0[w,k] = 1/V + u(w,k), normalised per word; f64 arithmetic rounded once, zero past K. CPU
+    tensors run :func:`oni355.ref.cvb0_spec.init` in float64, rounded to f32."""
+    from ..ref import cvb0_spec
+    K, KS = _cvb_ks(K, KS, "cvb0_init")
+    V, P = int(V), int(pair_word.numel())
+    _need(pair_word, torch.int32, "pair_word")
+    if V < 1 or V * K > 0xFFFFFFFF:
+        raise ValueError("cvb0_init: V ≥ 1 and V·K below 2^32")
+    if not _is_dev(pair_word):
+        return torch.from_numpy(cvb0_spec.init(pair_word.numpy(), V, K, KS).astype(np.float32))
+    r = torch.empty(P, KS, dtype=torch.float32, device=pair_word.device)
+    _lib.check(_lib.lib().oni_cvb0_init(_lib.ptr(pair_word) if P else None, P, V, KS, K, _lib.ptr(r) if P else None,
+                                        _lib.stream()), "oni_cvb0_init")
+    return r
+
+
+def cvb0_word_major(pair_word: torch.Tensor, pair_cnt: torch.Tensor, V: int):
+    """The word-major pair list the word counts are summed over with :func:`vem_wsum`, built once per
+    model: (word_pair_ptr int64 [V + 1], wm_src int32 [P], wm_word int32 [P], wm_cnt f32 [P]);
+    ``wm_src`` is the doc-major position of every word-major pair (the row of r it owns), ``wm_cnt``
+    its count. Stable sort: a word's pairs keep their document order. Then n_wk =
+    ``vem_wsum(r, wm_cnt, ones, word_pair_ptr, wm_src, wm_word, V, K)`` with ``ones`` f32 [V + 1, KS]."""
+    _need(pair_word, torch.int32, "pair_word")
+    _need(pair_cnt, torch.int32, "pair_cnt", int(pair_word.numel()))
+    wm_word, order = torch.sort(pair_word, stable=True)
+    ptr = torch.zeros(int(V) + 1, dtype=torch.int64, device=pair_word.device)
+    if pair_word.numel():
+        torch.cumsum(torch.bincount(pair_word.long(), minlength=int(V))[: int(V)], 0, out=ptr[1:])
+    return ptr, order.to(torch.int32), wm_word.contiguous(), pair_cnt[order].to(torch.float32)
+
+
+def cvb0_update(r: torch.Tensor, n_dk: torch.Tensor, n_wk: torch.Tensor, n_k: torch.Tensor, pair_doc: torch.Tensor,
+                pair_word: torch.Tensor, pair_cnt: torch.Tensor, doc_pair_ptr: torch.Tensor, K: int, alpha: float,
+                beta: float, V: int, grid: int | None = None) -> torch.Tensor:
+    """One batch (Jacobi) CVB0 step (k_cvb_update / k_cvb_update_wide, k_cvb_docs): every row of ``r``
+    f32 [P, KS] is replaced IN PLACE by the normalised (max(n_dk − r, 0) + α)(max(n_wk − r, 0) + β) /
+    (max(n_k − r, 0) + Vβ) of the old counts ``n_dk`` f32 [D, KS], ``n_wk`` f32 [V, KS], ``n_k`` f64
+    [KS]; returns the new document counts f32 [D, KS] = Σ_{p in d} c_p · r_p, summed in f64 and
+    rounded once. The pairs are doc-major int32 [P] (``pair_doc`` non-decreasing, ``doc_pair_ptr``
+    int64 [D + 1] their ranges). Pairs naming a document or word out of range keep their row and
+    contribute nothing. Same inputs, same bits, whatever ``grid`` (blocks per pass). CPU tensors run
+    :func:`oni355.ref.cvb0_spec.update` in float64, rounded to f32."""
+    from ..ref import cvb0_spec
+    _need(r, torch.float32, "r")
+    P, V, alpha, beta = int(pair_doc.numel()), int(V), float(alpha), float(beta)
+    if r.dim() != 2 or r.shape[0] != P:
+        raise ValueError("cvb0_update: r f32 [P, KS]")
+    K, KS = _cvb_ks(K, r.shape[1], "cvb0_update")
+    _need(n_dk, torch.float32, "n_dk")
+    _need(n_wk, torch.float32, "n_wk", V * KS)
+    _need(n_k, torch.float64, "n_k", KS)
+    if n_dk.dim() != 2 or n_dk.shape[1] != KS or V < 1:
+        raise ValueError("cvb0_update: n_dk f32 [D, KS], n_wk f32 [V, KS] with r's KS, V ≥ 1")
+    D, dev = int(n_dk.shape[0]), r.device
+    for t, nm in ((pair_doc, "pair_doc"), (pair_word, "pair_word"), (pair_cnt, "pair_cnt")):
+        _need(t, torch.int32, nm, P)
+    _need(doc_pair_ptr, torch.int64, "doc_pair_ptr", D + 1)
+    if any(t.device != dev for t in (n_dk, n_wk, n_k, pair_doc, pair_word, pair_cnt, doc_pair_ptr)):
+        raise ValueError("cvb0_update: every tensor must be on r's device")
+    if not (alpha > 0 and beta > 0):
+        raise ValueError("cvb0_update: alpha and beta must be > 0")
+    if grid is not None and not 1 <= int(grid) <= 65535:
+        raise ValueError("cvb0_update: grid must be in [1, 65535]")
+    if not _is_dev(r):
+        rn, nd = cvb0_spec.update(r.numpy(), n_dk.numpy(), n_wk.numpy(), n_k.numpy(), pair_doc.numpy(),
+                                  pair_word.numpy(), pair_cnt.numpy(), K, alpha, beta, V)
+        r.copy_(torch.from_numpy(rn.astype(np.float32)))
+        return torch.from_numpy(nd.astype(np.float32))
+    out = torch.empty(D, KS, dtype=torch.float32, device=dev)
+    # a head and a tail record of KS doubles per wave of 64 pairs: never initialised
+    scratch = torch.empty(max(2 * ((P + 63) // 64) * KS, 1), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().oni_cvb0_update(_lib.ptr(r) if P else None, _lib.ptr(n_dk) if D else None, _lib.ptr(n_wk),
+                                          _lib.ptr(n_k), _lib.ptr(pair_doc) if P else None,
+                                          _lib.ptr(pair_word) if P else None, _lib.ptr(pair_cnt) if P else None,
+                                          _lib.ptr(doc_pair_ptr), P, D, V, KS, K, alpha, beta,
+                                          _lib.ptr(out) if D else None, _lib.ptr(scratch), int(scratch.numel()),
+                                          int(grid or 0), _lib.stream()), "oni_cvb0_update")
+    return out
+
+
+def cvb0_theta(n_dk: torch.Tensor, doc_len: torch.Tensor, K: int, alpha: float) -> torch.Tensor:
+    """θ f32 [D, KS] = (n_dk + α)/(doc_len + Kα) from CVB0's document counts (k_cvb_theta), f64
+    arithmetic rounded once, zero past K; a document of length 0 gets 1/K. ``doc_len`` int64 [D].
+    CPU tensors run :func:`oni355.ref.cvb0_spec.theta` in float64, rounded to f32."""
+    from ..ref import cvb0_spec
+    _need(n_dk, torch.float32, "n_dk")
+    if n_dk.dim() != 2:
+        raise ValueError("cvb0_theta: n_dk f32 [D, KS]")
+    K, KS = _cvb_ks(K, n_dk.shape[1], "cvb0_theta")
+    D, alpha = int(n_dk.shape[0]), float(alpha)
+    _need(doc_len, torch.int64, "doc_len", D)
+    if doc_len.device != n_dk.device:
+        raise ValueError("cvb0_theta: every tensor must be on n_dk's device")
+    if not alpha > 0:
+        raise ValueError("cvb0_theta: alpha must be > 0")
+    if not _is_dev(n_dk):
+        return torch.from_numpy(cvb0_spec.theta(n_dk.numpy(), doc_len.numpy(), K, alpha).astype(np.float32))
+    theta = torch.empty(D, KS, dtype=torch.float32, device=n_dk.device)
+    _lib.check(_lib.lib().oni_cvb0_theta(_lib.ptr(n_dk) if D else None, _lib.ptr(doc_len) if D else None, D, KS, K,
+                                         alpha, _lib.ptr(theta) if D else None, _lib.stream()), "oni_cvb0_theta")
+    return theta

@@ -112,6 +112,10 @@ _REGISTRY: dict[str, list] = {
     "oni_vem_wsum": [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, vp, C.c_int, vp],
     "oni_vem_table": [vp, i64, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int, vp],
     "oni_vem_bound": [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp, i64, i64, C.c_double, vp, vp, vp, i64, C.c_int, vp],
+    "oni_cvb0_init": [vp, i64, i64, C.c_int, C.c_int, vp, vp],
+    "oni_cvb0_update": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, vp,
+                        vp, i64, C.c_int, vp],
+    "oni_cvb0_theta": [vp, vp, i64, C.c_int, C.c_int, C.c_double, vp, vp],
 }
 # argument structs whose size the library reports: checked against the mirrors above at load
 _ARG_STRUCTS = {"oni_gibbs_sizeof_args": OniGibbs, "oni_mh_sizeof_args": OniMH, "oni_foldin_sizeof_args": OniFoldin}

@@ -548,8 +548,11 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
                     ldac_lag: int = 0, word_ids: torch.Tensor | None = None, n_event0: int = 0,
                     on_train=None, method: str = "gibbs", em_iters: int = 30, var_iters: int = 20,
                     em_tol: float = 0.0, estimate_alpha: bool = False, var_tol: float = 0.0,
-                    warm_start: bool = False) -> LdaRun:
+                    warm_start: bool = False, cvb_iters: int = 100) -> LdaRun:
     """Token keys → owner routing → local corpus → Gibbs LDA trained for ``sweeps`` sweeps.
+
+    ``method`` ``"cvb0"`` trains by ``cvb_iters`` steps of batch CVB0 (models.cvb0_gpu.CvbLDA), under
+    the same restrictions as ``"vem"``.
 
     ``method`` ``"vem"`` trains the model by variational EM instead (models.vem_gpu.VarLDA:
     ``em_iters`` EM iterations of ``var_iters`` E-step iterations each, single GPU, no seed):
@@ -584,7 +587,7 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
         G, _ = tiling_for(K)
         mh = sampler_for(K) == "mh"
         # an MH model's first sweeps run the dense kernel on a corpus of the dense tiling
-        burn_mh = mh_burn_for(sweeps) if mh and train and method != "vem" else 0
+        burn_mh = mh_burn_for(sweeps) if mh and train and method not in ("vem", "cvb0") else 0
         Gd = tiling_for(K, "dense")[0] if burn_mh else G
         if chunk_len <= 0:
             # the global (weighted) token count picks L -- before routing: the placement cuts
@@ -640,6 +643,9 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
     if method == "vem":
         return _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters, var_iters, eval_every,
                           train, timer, log, on_train, em_tol, estimate_alpha, var_tol, warm_start)
+    if method == "cvb0":
+        return _train_cvb0(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, cvb_iters, eval_every, train,
+                           timer, log, on_train)
     # ONI_CHAINS = C > 1: C independent chains of sweeps // C sweeps each (same total sweep count),
     # scored by the average of their pair scores (LdaRun.pair_scores): the top-N then depends less
     # on any one chain's seed. Dense samplers only, no checkpointing.
@@ -728,10 +734,18 @@ def build_and_train(doc_keys64: torch.Tensor, word_keys64: torch.Tensor | None, 
 
 def check_train_method(method: str, em_iters: int, var_iters: int, comm=None, ckpt=None, ldac_dir=None,
                        em_tol: float = 0.0, estimate_alpha: bool = False, var_tol: float = 0.0,
-                       warm_start: bool = False) -> None:
-    """``method`` of run_* : ``"gibbs"`` or ``"vem"``; what vem training does not combine with."""
-    if method not in ("gibbs", "vem"):
-        raise ValueError(f"method must be 'gibbs' or 'vem', not {method!r}")
+                       warm_start: bool = False, cvb_iters: int = 100) -> None:
+    """``method`` of run_* : ``"gibbs"``, ``"vem"`` or ``"cvb0"``; what vem and cvb0 training do not
+    combine with."""
+    if method not in ("gibbs", "vem", "cvb0"):
+        raise ValueError(f"method must be 'gibbs', 'vem' or 'cvb0', not {method!r}")
+    if method == "cvb0":
+        if int(cvb_iters) < 0:
+            raise ValueError("cvb_iters must be ≥ 0")
+        if comm is not None and comm.dist:
+            raise NotImplementedError("cvb0 training is single-GPU")
+        if ckpt is not None or ldac_dir:
+            raise ValueError("cvb0 training writes no checkpoints and no lda-c snapshots")
     if method != "vem" and (em_tol or estimate_alpha):
         raise ValueError("em_tol and estimate_alpha belong to method='vem'")
     if method != "vem" and (var_tol or warm_start):
@@ -784,6 +798,31 @@ def _train_vem(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, em_iters
             on_train()
         model.run(em_iters, var_iters, eval_every=eval_every, log=log, em_tol=em_tol, estimate_alpha=estimate_alpha,
                   var_tol=var_tol, warm_start=warm_start)
+    model.close()
+    if not model.likelihoods or model.likelihoods[-1][0] != model.sweeps_done:
+        model.record_likelihood()
+    run.timings.update({"sweeps": model.sweeps_done, "chains": 1})
+    return run
+
+
+def cvb0_stats(method: str, cvb_iters: int) -> dict:
+    """What ``stats`` gains in cvb0 mode (nothing otherwise)."""
+    return {"train_method": "cvb0", "cvb_iters": int(cvb_iters)} if method == "cvb0" else {}
+
+
+def _train_cvb0(corpus, udoc, vocab, pairs, route, K, alpha, beta, comm, cvb_iters, eval_every, train, timer, log,
+                on_train) -> LdaRun:
+    """The ``init`` / ``train`` stages of :func:`build_and_train` with ``method="cvb0"``."""
+    from ..models.cvb0_gpu import CvbLDA
+    with timer.stage("init"):
+        model = CvbLDA(corpus, K, alpha, beta, comm=comm)
+        run = LdaRun(corpus, model, udoc, vocab, {}, pairs=pairs, route=route)
+        if not train:
+            return run
+    with timer.stage("train"):
+        if on_train is not None:
+            on_train()
+        model.run(cvb_iters, eval_every=eval_every, log=log)
     model.close()
     if not model.likelihoods or model.likelihoods[-1][0] != model.sweeps_done:
         model.record_likelihood()
@@ -1128,9 +1167,10 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
                           timer: StageTimer | None = None, ldac_dir: str | None = None,
                           ldac_lag: int = 0, key_bits: int = 64, method: str = "gibbs", em_iters: int = 30,
                           var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False,
-                          var_tol: float = 0.0, warm_start: bool = False) -> SingleResult:
+                          var_tol: float = 0.0, warm_start: bool = False, cvb_iters: int = 100) -> SingleResult:
     """Shared DNS/proxy path: one (doc, word) token per event; score = θ_doc·φ_word (C24)."""
-    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha, var_tol, warm_start)
+    check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha, var_tol, warm_start,
+                       cvb_iters)
     dev = doc_keys64.device
     timer = timer or StageTimer(dev)
     with timer.stage("vocab"):
@@ -1147,7 +1187,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     run = build_and_train(dk, None, wts, vocab, K, alpha, beta, seed, sweeps, chunk_len, comm, eval_every=eval_every, burnin=burnin,
                           ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag, word_ids=wids,
                           n_event0=n, method=method, em_iters=em_iters, var_iters=var_iters, em_tol=em_tol,
-                          estimate_alpha=estimate_alpha, var_tol=var_tol, warm_start=warm_start)
+                          estimate_alpha=estimate_alpha, var_tol=var_tol, warm_start=warm_start, cvb_iters=cvb_iters)
     hist = torch.zeros(2048, dtype=torch.int32, device=dev)
     if run.route is not None:
         with timer.stage("score_prep"):
@@ -1175,6 +1215,7 @@ def run_single_doc_events(doc_keys64: torch.Tensor, word_keys64: torch.Tensor, K
     stats.update({"events": int(doc_keys64.numel()),
                   "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
     stats.update(vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run, var_tol, warm_start))
+    stats.update(cvb0_stats(method, cvb_iters))
     return SingleResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(),
                         words=words.cpu().numpy().view(np.uint64), timings=t, stats=stats, lda=run)
 

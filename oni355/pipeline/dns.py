@@ -123,10 +123,10 @@ def run_dns(cols: dict, K: int = 50, sweeps: int = 200, tol: float = 1.0, maxres
             ckpt=None, log=None, ldac_dir: str | None = None, ldac_lag: int = 0,
             device_cols: dict | None = None, method: str = "gibbs", em_iters: int = 30,
             var_iters: int = 20, em_tol: float = 0.0, estimate_alpha: bool = False,
-            var_tol: float = 0.0, warm_start: bool = False) -> common.SingleResult:
+            var_tol: float = 0.0, warm_start: bool = False, cvb_iters: int = 100) -> common.SingleResult:
     """``device_cols``: :func:`host_arrays` already on the device (e.g. prefetched by
     io.staging.Prefetcher while the previous day computed). ``method`` / ``em_iters`` /
-    ``var_iters`` / ``em_tol`` / ``estimate_alpha`` / ``var_tol`` / ``warm_start``: ``"vem"`` trains by variational EM, see :func:`oni355.pipeline.flow.run_flow`."""
+    ``var_iters`` / ``em_tol`` / ``estimate_alpha`` / ``var_tol`` / ``warm_start``: ``"vem"`` trains by variational EM, ``"cvb0"`` by ``cvb_iters`` steps of batch CVB0, see :func:`oni355.pipeline.flow.run_flow`."""
     timer = StageTimer(device)
     with timer.stage("h2d"):
         d = dict(device_cols) if device_cols is not None else to_device(cols, device)
@@ -151,7 +151,7 @@ def run_dns(cols: dict, K: int = 50, sweeps: int = 200, tol: float = 1.0, maxres
                                        timer=timer, ldac_dir=ldac_dir, ldac_lag=ldac_lag,
                                        key_bits=40, method=method, em_iters=em_iters, var_iters=var_iters,
                                        em_tol=em_tol, estimate_alpha=estimate_alpha, var_tol=var_tol,
-                                       warm_start=warm_start)
+                                       warm_start=warm_start, cvb_iters=cvb_iters)
     res.stats["cuts"] = {k: [int(x) for x in v] for k, v in cuts.items()}
     res.stats["features"] = feats
     return res

@@ -227,7 +227,8 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
              row_offset: int = 0, eval_every: int = 0, burnin: int = 0, ckpt=None, log=None, ldac_dir: str | None = None,
              ldac_lag: int = 0, device_cols: dict | None = None, on_train=None, method: str = "gibbs",
              em_iters: int = 30, var_iters: int = 20, em_tol: float = 0.0,
-             estimate_alpha: bool = False, var_tol: float = 0.0, warm_start: bool = False) -> FlowResult:
+             estimate_alpha: bool = False, var_tol: float = 0.0, warm_start: bool = False,
+             cvb_iters: int = 100) -> FlowResult:
     """Full suspicious-connects for one (rank-local shard of a) day of flows. ``device_cols``:
     the day's :data:`DEVICE_COLS` already on the device (e.g. from io.staging.Prefetcher, which
     uploaded them while the previous day computed); ``cols`` still supplies the host rows.
@@ -242,7 +243,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
     maximum), ``warm_start`` starts every EM iteration's E-step from the previous one's γ; with either,
     ``stats`` carries both and ``var_iters_mean_first`` / ``var_iters_mean_last``."""
     common.check_train_method(method, em_iters, var_iters, comm, ckpt, ldac_dir, em_tol, estimate_alpha, var_tol,
-                              warm_start)
+                              warm_start, cvb_iters)
     timer = StageTimer(device)
     if device_cols is None:
         cols, feedback = with_ipv6_keys(cols, comm, (feedback,)) if feedback else (with_ipv6_keys(cols, comm), None)
@@ -280,7 +281,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
                                  eval_every=eval_every, burnin=burnin, ckpt=ckpt, log=log, timer=timer, ldac_dir=ldac_dir,
                                  ldac_lag=ldac_lag, word_ids=wids, n_event0=n, on_train=on_train, method=method,
                                  em_iters=em_iters, var_iters=var_iters, em_tol=em_tol, estimate_alpha=estimate_alpha,
-                                 var_tol=var_tol, warm_start=warm_start)
+                                 var_tol=var_tol, warm_start=warm_start, cvb_iters=cvb_iters)
 
     # ---- scoring --------------------------------------------------------------------------------
     hist = torch.zeros(2048, dtype=torch.int32, device=d["sip"].device)
@@ -337,6 +338,7 @@ def run_flow(cols: dict, K: int = 20, sweeps: int = 200, tol: float = 1.0, maxre
     stats = run.corpus.stats()
     stats.update({"n_flows": n, "loglik": run.model.likelihoods[-1][1] if run.model.likelihoods else None})
     stats.update(common.vem_stats(method, em_iters, var_iters, em_tol, estimate_alpha, run, var_tol, warm_start))
+    stats.update(common.cvb0_stats(method, cvb_iters))
     return FlowResult(rows=rows.cpu().numpy(), scores=scs.cpu().numpy(), src_scores=parts[:, 0].cpu().numpy(),
                       dst_scores=parts[:, 1].cpu().numpy(), src_words=wparts[:, 0].cpu().numpy().view(np.uint32),
                       dst_words=wparts[:, 1].cpu().numpy().view(np.uint32), cuts=cuts, timings=t, stats=stats,
